@@ -258,6 +258,25 @@ int pcd_denoiser_lists(pcd_denoiser* dn, int64_t* out, int cols, void* stream);
  * smallest eigenvalue's eigenvector) come out through pcd_denoiser_store. */
 int pcd_denoiser_set_probe(pcd_denoiser* dn, int enable);
 int pcd_denoiser_probe_store(pcd_denoiser* dn, float* nvt2_eig4, void* stream);
+/* Exact NVT2 (default OFF; no allocation).  The default NVT2 stage leaves the tensor unnormalised and solves it with
+ * a fixed-sweep Jacobi: its classes match the reference, its edge vectors are LAPACK's only to ~5e-7/gap, with an
+ * arbitrary sign.  While ON, every NVT2 stage (iterate, pcd_denoiser_stage, pcd_slab_iterate) runs the reference's
+ * second vote as it runs the first (Processor.py:110-117: getBetterFilteredNVT on the filtered normals,
+ * Decompositionor.py:278-300): T / Σw and LAPACK's ssyevd, the arithmetic of NVT1, bit for bit.  store()'s
+ * edge_vectors are then eigvec[..., 0] with LAPACK's sign, and probe_store's eigenvalues are those of T / Σw as
+ * computed, not a quotient.  Costs NVT2 time; pcd_denoise_params is unchanged. */
+int pcd_denoiser_set_exact_nvt2(pcd_denoiser* dn, int enable);
+/* Processor.getMyFeatureDecomposition (Processor.py:110-117) on the loaded state from the fused stages: K1 (the kNN
+ * of the current positions, NVT1, VU smoothing -> f_n) and the exact NVT2 on f_n (Decompositionor.py:278-300),
+ * whatever set_exact_nvt2 says.  Outputs in caller order, each nullable: eigval [N][3] ascending, eigvec [N][3][3]
+ * (columns: eigvec[i][r][c] = component r of eigenvector c, pcd_nvt_csr's layout), f_n [N][3], classes int64 [N]
+ * (p->class_scale).  Uses p->k, k_update (the stored list length), rho, tau, damp, class_scale; same limits and
+ * argument checks as iterate.  It moves no position, does not rebind the normals and leaves the classes / edge
+ * vectors of the last iteration alone: an iterate() after it computes what it would have computed without it.
+ * pcd_denoiser_lists then returns this call's kNN lists, and the probe (when on) its eigenvalues and Σw.  Working buffers ([N] x 49 B) are allocated on the first
+ * call and freed at destroy.  Ends with pcd_denoiser_check (synchronises `stream`). */
+int pcd_denoiser_decompose(pcd_denoiser* dn, const pcd_denoise_params* p, float* eigval, float* eigvec, float* f_n,
+                           int64_t* classes, void* stream);
 
 /* ---- spatial slabs (multi-GPU): the same loop over a rank's own points with a halo ----
  * The grid holds the rank's points plus halo snapshot points owned by other ranks.  Only the ACTIVE rows are

@@ -3,8 +3,10 @@
 `denoise()` / `denoiseUntilMinimumError()` run the loop body of the reference (Processor.py:119-185) as the fused
 libpcd loop (pcd_denoiser_*): kNN+NVT1+smoothing, NVT2+classes, then the class phases Gauss-Seidel in order, all on
 device buffers in spatial order; results are written back into the caller's tensors with the reference's aliasing
-(graph.pos mutated in place, graph.n rebound to f_n).  `getMyFeatureDecomposition()` keeps the op-by-op path
-(Selector -> Decompositionor) because it must return the full Decomposition.
+(graph.pos mutated in place, graph.n rebound to f_n).  `exact_nvt2=True` runs the second normal vote with the
+reference's arithmetic (pcd_denoiser_set_exact_nvt2).  `getMyFeatureDecomposition()` runs op by op (Selector ->
+Decompositionor) by default; `fused=True` returns the same Decomposition, bit for bit, from the fused stages
+(pcd_denoiser_decompose: no int64 CSR, one library call).
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ from typing import Callable
 import torch
 
 import pcd_native as _nat
-from .Decompositionor import Decompositionor
+from .Decompositionor import Decomposition, Decompositionor
 from .Denoiser import STEP_KINDS, Denoiser
 from .GraphBuilder import GraphBuilder
 from .Noise import Noise
@@ -39,9 +41,18 @@ class Processor:
         self._fused = None
 
     # ------------------------------------------------------------------ op-by-op feature decomposition
-    def getMyFeatureDecomposition(self, N: int = 2 ** 4, angle: float = None):
+    def getMyFeatureDecomposition(self, N: int = 2 ** 4, angle: float = None, fused: bool = False):
+        """Processor.py:110-117.  fused: the same (Decomposition, f_n) from the fused loop's stages."""
         angle = angle if angle is not None else DEFAULT_ANGLE
         n = self.graph.n
+        if fused:
+            g = self.graph
+            GeneralUtils.validateAttributes(g, ["pos", "n"])
+            dn = self._fused_for(N)
+            dn.load(g.pos, n)
+            eigval, eigvec, f_n = dn.decompose(_nat.make_params(k=N, k_update=N, rho=angle))
+            dev, dt = g.pos.device, g.pos.dtype
+            return Decomposition(eigval.to(dev), eigvec.to(dev)), f_n.to(device=dev, dtype=dt)
         selection = self.selector.getKNNSelection(N)
         nvt = self.decompositionor.getBetterFilteredNVT(selection, n, angle)
         filtered_normals = nvt.getVUSmoothedNormals(n)
@@ -85,10 +96,11 @@ class Processor:
         return TorchUtils.averageEdgeLength(self.graph.pos, self.selector.getKNNSelection(6).getEdgeIndex())
 
     def _run_fused(self, iterations: int, k: int, k_update: int, d: float, phases, angle=None,
-                   return_classes: bool = False):
+                   return_classes: bool = False, exact_nvt2: bool = False):
         g = self.graph
         GeneralUtils.validateAttributes(g, ["pos", "n"])
         fused = self._fused_for(max(k, k_update))
+        fused.set_exact_nvt2(exact_nvt2)
         fused.load(g.pos, g.n)
         params = _nat.make_params(k=k, k_update=k_update, rho=angle, d=float(d), phases=phases)
         fused.iterate(params, iterations)
@@ -103,15 +115,17 @@ class Processor:
         return cls
 
     def denoise(self, iterations: int = 2, k: int = 2 ** 4, k_update: int = 8, alphas=DEFAULT_ALPHAS,
-                d: float = None, angle: float = None):
-        """Processor.py:119-139.  Defaults reproduce the reference exactly (k=16, k_u=8, 2 iterations, d=2l)."""
+                d: float = None, angle: float = None, exact_nvt2: bool = False):
+        """Processor.py:119-139.  Defaults reproduce the reference exactly (k=16, k_u=8, 2 iterations, d=2l).
+        exact_nvt2: the second vote's eigen-decomposition as LAPACK computes it (pcd_denoiser_set_exact_nvt2)."""
         if d is None:
             d = 2 * float(self.meanEdgeLength())
         phases = ((0, _nat.STEP_FLAT, alphas[0]), (1, _nat.STEP_EDGE, alphas[1]), (2, _nat.STEP_FEATURE, alphas[2]))
-        self._run_fused(iterations, k, k_update, d, phases, angle)
+        self._run_fused(iterations, k, k_update, d, phases, angle, exact_nvt2=exact_nvt2)
 
     def thesisDenoise(self, iterations: int = 2, alphas=DEFAULT_ALPHAS, d: float = None,
-                      step_clamp_factor: float = 20000.0, k: int = 2 ** 4, k_update: int = 8, angle: float = None):
+                      step_clamp_factor: float = 20000.0, k: int = 2 ** 4, k_update: int = 8, angle: float = None,
+                      exact_nvt2: bool = False):
         """The thesis-results driver ("Ours", PostProcessing.ipynb:1069-1090): per iteration the feature decomposition,
         then flat_step (alpha[0]) on flat points and feature_step (alphas[1], alphas[2]) on edge and corner points, all
         computed from the iteration's input positions (Jacobi across classes: temp_pos = pos.clone()), with the per-step
@@ -124,6 +138,7 @@ class Processor:
         g = self.graph
         GeneralUtils.validateAttributes(g, ["pos", "n"])
         fused = self._fused_for(max(k, k_update))
+        fused.set_exact_nvt2(exact_nvt2)
         fused.load(g.pos, g.n)
         params = _nat.make_params(k=k, k_update=k_update, rho=angle, d=float(d) * step_clamp_factor, phases=phases,
                                   jacobi=True, clamp_global=float(d))
@@ -191,7 +206,8 @@ class Processor:
 
     def denoiseUntilMinimumError(self, gt_pos: torch.Tensor, strategy: dict, k: int = 7,
                                  alpha: list = [0.02, 0.02, 0.1], d: float = 200,
-                                 error_funcs: list[Callable] = [TorchUtils.PaperDistance], N: int = 2 ** 4):
+                                 error_funcs: list[Callable] = [TorchUtils.PaperDistance], N: int = 2 ** 4,
+                                 exact_nvt2: bool = False):
         """Processor.py:141-185: iterate while error_funcs[0] decreases; same object flow for the returned tensor."""
         _graph = self.graph
         phases = []
@@ -208,7 +224,7 @@ class Processor:
         previous_error = [f(gt_pos, _graph.pos) + 200 for f in error_funcs]
         current_error = [f(gt_pos, _graph.pos) for f in error_funcs]
         while current_error[0].mean(dim=0) < previous_error[0].mean(dim=0):
-            self._run_fused(1, N, k, d, phases)
+            self._run_fused(1, N, k, d, phases, exact_nvt2=exact_nvt2)
             error = [f(gt_pos, _graph.pos) for f in error_funcs]
             previous_error = current_error
             current_error = error

@@ -651,6 +651,47 @@ __global__ __launch_bounds__(kNvtBS, PCD_NVT2_OCC) void k_nvt2(const float4* __r
     }
 }
 
+// K2, exact mode (pcd_denoiser_set_exact_nvt2, pcd_denoiser_decompose): the reference's second vote restated as its
+// first (Processor.py:110-117: getBetterFilteredNVT on the filtered normals) -- the tensor normalised by Σw and
+// LAPACK's ssyevd (eigh3), NVT1's arithmetic bit for bit.  Same windows, row selection, block mapping and list
+// loading as k_nvt2.  w are the eigenvalues of T / Σw themselves; the edge vector is the first eigenvector column
+// with LAPACK's sign.  edge is nullable.  full (nullable, pcd_denoiser_decompose): three planes of N float4 rows holding the row's
+// twelve floats (w0 w1 w2 V00 | V01 V02 V10 V11 | V12 V20 V21 V22), one coalesced 16-B store per plane.
+// 8 neighbours in flight per batch, as k_nvt2 (A/B at 10M, k = 32: 2 / 4 / 8 -> 1.111 / 1.045 / 1.015 ms; a 5-wave
+// launch bound spills 176 B).
+template <int K>
+__global__ __launch_bounds__(kNvtBS, PCD_NVT2_OCC) void k_nvt2_exact(const float4* __restrict__ pos, const float4* __restrict__ fn,
+                                               const int32_t* __restrict__ idx, int64_t N, RowMap rm, int k,
+                                               float rho, float scale, uint8_t* __restrict__ cls,
+                                               float4* __restrict__ edge, int win, float4* __restrict__ probe,
+                                               float4* __restrict__ full, RowSel sel) {
+    __shared__ float4 s_pos[WinSize<kWinHaloNvt2, kNvtBS>::rows], s_fn[WinSize<kWinHaloNvt2, kNvtBS>::rows];
+    const int64_t b0 = xcd_block(blockIdx.x, gridDim.x) * blockDim.x;
+    const int64_t t0 = b0 + threadIdx.x;
+    const bool mine = t0 < rm.nq && sel.take(t0);
+    if (sel.flag && !__syncthreads_or(mine)) return;     // (block-uniform: a pass skips the blocks it has no row in)
+    const int64_t lo = stage_window<kWinHaloNvt2, kNvtBS>(pos, fn, N, rm(b0), s_pos, s_fn, win);
+    if (!mine) return;
+    const int64_t i = rm(t0);
+    const float4 p4 = pos[i];
+    int wsum = 0;
+    int l[K];
+    load_list<K, true>(idx, N, i, k, l);
+    const Sym3 T = nvt_tensor<K, true, true>(WinRows<kWinHaloNvt2, kNvtBS>{pos, s_pos, lo}, WinRows<kWinHaloNvt2, kNvtBS>{fn, s_fn, lo},
+                                                v3(p4.x, p4.y, p4.z), k, RegNb32{l}, rho, BlkNbSafe{idx, N, i},
+                                                &wsum);
+    float w[3], V[3][3];
+    eigh3(T, w, V);
+    cls[i] = (uint8_t)classify(w, scale, nullptr);
+    if (edge) store4(edge, i, v3(V[0][0], V[1][0], V[2][0]));
+    if (probe) probe[i] = make_float4(w[0], w[1], w[2], (float)wsum);
+    if (full) {
+        full[i] = make_float4(w[0], w[1], w[2], V[0][0]);
+        full[N + i] = make_float4(V[0][1], V[0][2], V[1][0], V[1][1]);
+        full[2 * N + i] = make_float4(V[1][2], V[2][0], V[2][1], V[2][2]);
+    }
+}
+
 // One flat-reduction block's partial: f64 sums and count of its rows, the box of those rows (for the pruned max
 // distance pass), and whether that pass must scan the block (set by k_centre).
 struct RedC { double sx, sy, sz, cnt; float lo[3], hi[3]; int scan, pad; };
@@ -916,6 +957,26 @@ __global__ void k_scatter4(const float4* __restrict__ src, const int32_t* __rest
     if (r < N) out[perm[r]] = src[r];
 }
 
+// pcd_denoiser_decompose: k_nvt2_exact's three planes, f_n and the classes -> caller order (every output nullable)
+__global__ void k_decomp_store(const float4* __restrict__ full, const float4* __restrict__ fn_s,
+                               const uint8_t* __restrict__ cls_s, const int32_t* __restrict__ perm, int64_t N,
+                               float* __restrict__ eigval, float* __restrict__ eigvec, float* __restrict__ fn,
+                               int64_t* __restrict__ cls) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const int64_t i = perm[r];
+    if (eigval || eigvec) {
+        const float4 a = full[r], b = full[N + r], c = full[2 * N + r];
+        if (eigval) { eigval[3 * i] = a.x; eigval[3 * i + 1] = a.y; eigval[3 * i + 2] = a.z; }
+        if (eigvec) {
+            float* v = eigvec + 9 * i;
+            v[0] = a.w; v[1] = b.x; v[2] = b.y; v[3] = b.z; v[4] = b.w; v[5] = c.x; v[6] = c.y; v[7] = c.z; v[8] = c.w;
+        }
+    }
+    if (fn) { const float4 f = fn_s[r]; fn[3 * i] = f.x; fn[3 * i + 1] = f.y; fn[3 * i + 2] = f.z; }
+    if (cls) cls[i] = cls_s[r];
+}
+
 // pcd_denoiser_lists: blocked sorted-order lists -> caller rows of original indices
 __global__ void k_lists(const int32_t* __restrict__ idx, const int32_t* __restrict__ perm, int64_t N, int cols,
                         int64_t* __restrict__ out) {
@@ -989,6 +1050,10 @@ struct pcd_denoiser {
     bool unit_nrm = false;        // nrm holds the loop's own normalised f_n (set by finish, cleared by load / writes)
     int windows = 1;              // LDS row windows in NVT1 / NVT2 / the flat phase (pcd_denoiser_set_windows)
     float4* probe = nullptr;      // NVT2 parity probe (pcd_denoiser_set_probe): normalised eigenvalues + Σw per row
+    bool exact_nvt2 = false;      // NVT2 as the reference computes it: T / Σw and LAPACK's eigh (pcd_denoiser_set_exact_nvt2)
+    float4* dfull = nullptr;      // pcd_denoiser_decompose: 3 planes of N rows (k_nvt2_exact), allocated on first use
+    uint8_t* dcls = nullptr;      // pcd_denoiser_decompose: its classes (the loop's cls / edge stay the last iteration's)
+    bool k1_lists = false;        // the stored lists are a K1 stage's of the loaded state (decompose; pcd_denoiser_lists)
     bool loaded = false, iterated = false;
     bool timing = false;
     bool timing_k1 = false;       // level 2: only the K1 stage's two events (the bench's timed region)
@@ -1060,10 +1125,11 @@ static int check_params(const pcd_denoiser* dn, const pcd_denoise_params* p) {
     return PCD_OK;
 }
 
-static int list_cap(const pcd_denoise_params* p) {
-    const int kstore = std::max(p->k, p->k_update);
-    return kstore <= 8 ? 8 : kstore <= 16 ? 16 : kstore <= 32 ? 32 : 64;
-}
+// Columns the kernels address for a list of kstore entries: whole 8-column blocks (pcd_lists.h), on the ladder of the
+// kernel instantiations.  The stored lists and the anchor sets are ALLOCATED by this, not by knn_cap (the register
+// top-k ladder, which has a 13: a k_max of 9..13 would get 13 N entries for lists whose second block ends at 16 N).
+static int list_cols_cap(int kstore) { return kstore <= 8 ? 8 : kstore <= 16 ? 16 : kstore <= 32 ? 32 : 64; }
+static int list_cap(const pcd_denoise_params* p) { return list_cols_cap(std::max(p->k, p->k_update)); }
 
 static bool phase_is_global(const pcd_denoise_params* p, int ph) {
     return p->phase_kind[ph] == PCD_STEP_FLAT || p->phase_kind[ph] == PCD_STEP_NEW;
@@ -1087,7 +1153,7 @@ static int stage_k1_anchored(pcd_denoiser* dn, const pcd_denoise_params* p, int 
     const int KA = 2 * K;
     if (!dn->anc) {
         if (hipMalloc(&dn->anc, N * sizeof(float4)) != hipSuccess ||
-            hipMalloc(&dn->alist, (int64_t)2 * knn_cap(dn->kcap) * N * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc(&dn->alist, (int64_t)2 * list_cols_cap(dn->kcap) * N * sizeof(int32_t)) != hipSuccess ||
             hipMalloc(&dn->redo, N * sizeof(int32_t)) != hipSuccess ||
             hipMalloc(&dn->spill, N * sizeof(int32_t)) != hipSuccess || hipMalloc(&dn->fail, N) != hipSuccess ||
             hipMalloc(&dn->rqs, sizeof(RqStats)) != hipSuccess)
@@ -1224,14 +1290,20 @@ static int stage_nvt1(pcd_denoiser* dn, const pcd_denoise_params* p, hipStream_t
     return PCD_OK;
 }
 
-static int stage_k2(pcd_denoiser* dn, const pcd_denoise_params* p, hipStream_t st, RowSel sel = RowSel{nullptr, 0}) {
+// NVT2 of the rows `sel` takes.  Default: k_nvt2 (unnormalised tensor, eigh3_min).  Exact mode
+// (pcd_denoiser_set_exact_nvt2), or dec (pcd_denoiser_decompose: classes to dcls, all twelve floats to dfull, the
+// loop's classes / edge vectors untouched; the probe, when on, is written as by any NVT2 stage): k_nvt2_exact.
+static int stage_k2(pcd_denoiser* dn, const pcd_denoise_params* p, hipStream_t st, RowSel sel = RowSel{nullptr, 0},
+                    bool dec = false) {
     const RowMap rm = dn->rowmap();
     if (rm.nq == 0) return PCD_OK;
     const dim3 blk(kNvtBS), grd((unsigned)cdiv(rm.nq, kNvtBS));
     float4* P = dn->pos[dn->cur];
 #define PCD_K2(C) \
     case C:                                                                                                            \
-        hipLaunchKernelGGL((k_nvt2<C>), grd, blk, 0, st, P, dn->fn, dn->idx, dn->n, rm, p->k, p->rho, p->class_scale, dn->cls, dn->edge, dn->windows, dn->probe, sel); \
+        if (dec) hipLaunchKernelGGL((k_nvt2_exact<C>), grd, blk, 0, st, P, dn->fn, dn->idx, dn->n, rm, p->k, p->rho, p->class_scale, dn->dcls, (float4*)nullptr, dn->windows, dn->probe, dn->dfull, sel); \
+        else if (dn->exact_nvt2) hipLaunchKernelGGL((k_nvt2_exact<C>), grd, blk, 0, st, P, dn->fn, dn->idx, dn->n, rm, p->k, p->rho, p->class_scale, dn->cls, dn->edge, dn->windows, dn->probe, (float4*)nullptr, sel); \
+        else hipLaunchKernelGGL((k_nvt2<C>), grd, blk, 0, st, P, dn->fn, dn->idx, dn->n, rm, p->k, p->rho, p->class_scale, dn->cls, dn->edge, dn->windows, dn->probe, sel); \
         break;
     switch (list_cap(p)) {
         PCD_K2(8) PCD_K2(16) PCD_K2(32) PCD_K2(64)
@@ -1368,7 +1440,7 @@ int pcd_denoiser_create(const pcd_grid* g, int k_max, pcd_denoiser** out) {
               hipMalloc(&dn->fn, N * sizeof(float4)) == hipSuccess &&
               hipMalloc(&dn->edge, N * sizeof(float4)) == hipSuccess &&
               hipMalloc(&dn->orig, N * sizeof(float4)) == hipSuccess &&
-              hipMalloc(&dn->idx, (int64_t)knn_cap(k_max) * N * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc(&dn->idx, (int64_t)list_cols_cap(k_max) * N * sizeof(int32_t)) == hipSuccess &&
               hipMalloc(&dn->cls, N) == hipSuccess &&
               hipMalloc(&dn->part, kNumPart * sizeof(RedC)) == hipSuccess &&
               hipMalloc(&dn->red, 16 * sizeof(double)) == hipSuccess &&
@@ -1393,6 +1465,7 @@ int pcd_denoiser_destroy(pcd_denoiser* dn) {
     (void)hipFree(dn->red); (void)hipFree(dn->gscal); (void)hipFree(dn->err);
     (void)hipFree(dn->anc); (void)hipFree(dn->alist); (void)hipFree(dn->redo); (void)hipFree(dn->spill);
     (void)hipFree(dn->rqs); (void)hipFree(dn->fail); (void)hipFree(dn->probe);
+    (void)hipFree(dn->dfull); (void)hipFree(dn->dcls);
     for (auto e : dn->ev) (void)hipEventDestroy(e);
     delete dn;
     return PCD_OK;
@@ -1410,6 +1483,7 @@ int pcd_denoiser_load(pcd_denoiser* dn, const float* pos, const float* n, void* 
     dn->iterated = false;
     dn->unit_nrm = false;         // the caller's normals: the general vote margin until the first finish
     dn->seed_cols = 0;
+    dn->k1_lists = false;
     return PCD_OK;
 }
 
@@ -1545,7 +1619,8 @@ int pcd_denoiser_status(pcd_denoiser* dn, int* bits, void* stream) {
 
 int pcd_denoiser_lists(pcd_denoiser* dn, int64_t* out, int cols, void* stream) {
     PCD_CHECK_ARG(dn && out, "null argument");
-    PCD_CHECK_ARG(dn->iterated && cols >= 1 && cols <= dn->list_cols, "cols must be in [1, stored list length]");
+    PCD_CHECK_ARG((dn->iterated || dn->k1_lists) && cols >= 1 && cols <= dn->list_cols,
+                  "cols must be in [1, stored list length]");
     if (settle(dn, as_stream(stream)) != PCD_OK) return PCD_ERR_HIP;
     hipLaunchKernelGGL(k_lists, dim3((unsigned)cdiv(dn->n, 256)), dim3(256), 0, as_stream(stream), dn->idx,
                        dn->g->perm, dn->n, cols, out);
@@ -1616,6 +1691,40 @@ int pcd_denoiser_probe_store(pcd_denoiser* dn, float* nvt2_eig4, void* stream) {
                        dn->g->perm, dn->n, reinterpret_cast<float4*>(nvt2_eig4));
     PCD_LAUNCH_CHECK();
     return PCD_OK;
+}
+
+int pcd_denoiser_set_exact_nvt2(pcd_denoiser* dn, int enable) {
+    PCD_CHECK_ARG(dn != nullptr, "null denoiser");
+    dn->exact_nvt2 = enable != 0;
+    return PCD_OK;
+}
+
+int pcd_denoiser_decompose(pcd_denoiser* dn, const pcd_denoise_params* p, float* eigval, float* eigvec, float* f_n,
+                           int64_t* classes, void* stream) {
+    int rc = check_params(dn, p);
+    if (rc != PCD_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if ((rc = settle(dn, st)) != PCD_OK) return rc;
+    if (!dn->dfull) {
+        if (hipMalloc(&dn->dfull, 3 * dn->n * sizeof(float4)) != hipSuccess || hipMalloc(&dn->dcls, dn->n) != hipSuccess) {
+            (void)hipFree(dn->dfull); (void)hipFree(dn->dcls);
+            dn->dfull = nullptr; dn->dcls = nullptr;
+            return fail(PCD_ERR_OOM, "pcd_denoiser_decompose: working buffers");
+        }
+        // rows outside the active set (pcd_denoiser_set_rows) are never written: NaN / class 255
+        PCD_HIP(hipMemsetAsync(dn->dfull, 0xFF, 3 * dn->n * sizeof(float4), st));
+        PCD_HIP(hipMemsetAsync(dn->dcls, 0xFF, dn->n, st));
+    }
+    // K1 on the current positions and normals (the kNN lists, NVT1, VU smoothing -> fn, the loop's scratch field that
+    // the next K1 rewrites), then the exact NVT2 on fn.  No phase runs and finish is not called: positions, normals,
+    // and the classes / edge vectors store() returns stay what they were.
+    if ((rc = stage_k1(dn, p, st)) != PCD_OK) return rc;
+    if ((rc = stage_k2(dn, p, st, RowSel{nullptr, 0}, true)) != PCD_OK) return rc;
+    dn->k1_lists = true;
+    hipLaunchKernelGGL(k_decomp_store, dim3((unsigned)cdiv(dn->n, 256)), dim3(256), 0, st, dn->dfull, dn->fn, dn->dcls,
+                       dn->g->perm, dn->n, eigval, eigvec, f_n, classes);
+    PCD_LAUNCH_CHECK();
+    return pcd_denoiser_check(dn, stream);
 }
 
 int pcd_denoiser_set_seeding(pcd_denoiser* dn, int enable) {

@@ -101,6 +101,9 @@ _SIGS = {
     "pcd_denoiser_lists": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "pcd_denoiser_set_probe": (c_int, [c_void_p, c_int]),
     "pcd_denoiser_probe_store": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pcd_denoiser_set_exact_nvt2": (c_int, [c_void_p, c_int]),
+    "pcd_denoiser_decompose": (c_int, [c_void_p, POINTER(DenoiseParams), c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
     "pcd_denoiser_set_rows": (c_int, [c_void_p, c_void_p, c_int64]),
     "pcd_denoiser_set_coverage": (c_int, [c_void_p, c_void_p, c_void_p]),
     "pcd_denoiser_set_coverage_spheres": (c_int, [c_void_p, c_void_p, c_void_p]),
@@ -359,6 +362,23 @@ class FusedDenoiser:
         out = torch.empty((self.grid.n, 4), dtype=torch.float32, device=device())
         check(lib().pcd_denoiser_probe_store(self.handle, ptr(out), c_void_p(stream_ptr())), "pcd_denoiser_probe_store")
         return out
+
+    def set_exact_nvt2(self, enable=True):
+        """NVT2 as the reference computes it (T / Σw, LAPACK's eigh: edge vectors with LAPACK's sign) on / off
+        (pcd_denoiser_set_exact_nvt2; off by default)."""
+        check(lib().pcd_denoiser_set_exact_nvt2(self.handle, int(bool(enable))), "pcd_denoiser_set_exact_nvt2")
+
+    def decompose(self, params: DenoiseParams, want_classes: bool = False):
+        """getMyFeatureDecomposition of the loaded state from the fused stages (pcd_denoiser_decompose):
+        (eigval [N, 3], eigvec [N, 3, 3], f_n [N, 3][, classes int64 [N]]), caller order.  Moves nothing."""
+        N, dev = self.grid.n, device()
+        eigval = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        eigvec = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
+        f_n = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        cls = torch.empty(N, dtype=torch.int64, device=dev) if want_classes else None
+        check(lib().pcd_denoiser_decompose(self.handle, ctypes.byref(params), ptr(eigval), ptr(eigvec), ptr(f_n),
+                                           ptr(cls), c_void_p(stream_ptr())), "pcd_denoiser_decompose")
+        return (eigval, eigvec, f_n, cls) if want_classes else (eigval, eigvec, f_n)
 
     def set_seeding(self, enable=True):
         check(lib().pcd_denoiser_set_seeding(self.handle, int(bool(enable))), "pcd_denoiser_set_seeding")

@@ -282,7 +282,8 @@ class LocalTransport:
 class HipSlabEngine:
     """libpcd's fused loop over one rank's local snapshot (owned + halo), driven stage by stage."""
 
-    def __init__(self, local_pos, local_n, owned_local, k_max, origin, cell, coverage, seeding=True, spheres=None):
+    def __init__(self, local_pos, local_n, owned_local, k_max, origin, cell, coverage, seeding=True, spheres=None,
+                 exact_nvt2=False):
         dev = nat.device()
         self.device = dev
         self.grid = nat.Grid(local_pos.to(dev), cell=cell, origin=origin)
@@ -293,6 +294,7 @@ class HipSlabEngine:
         self.fused = nat.FusedDenoiser(self.grid, k_max)
         self.fused.load(local_pos.to(dev), local_n.to(dev))
         self.fused.set_seeding(seeding)
+        self.fused.set_exact_nvt2(exact_nvt2)      # NVT2 as the reference computes it (pcd_denoiser_set_exact_nvt2)
         own_rows = torch.sort(self.row_of[owned_local.to(dev)]).values.to(torch.int32)
         # every local point owned (one rank): all rows, no row list (the single-GPU launch shapes)
         self.fused.set_rows(None if own_rows.numel() == self.n else own_rows)
@@ -452,7 +454,7 @@ class SlabDenoiser:
 
     def __init__(self, snap_pos, snap_n, k_max, transport=None, halo=None, engine_factory=None, seeding=True,
                  k_hint=None, check_every=1, halo_growth=2.0, max_replans=4, weights=None, native=None,
-                 sphere_quantile=0.999, step_bound=None, horizon=None):
+                 sphere_quantile=0.999, step_bound=None, horizon=None, exact_nvt2=False):
         """native: one pcd_slab_iterate call per iteration over libpcd's own transport (default for the HIP engine);
         False: the same stages driven from Python over torch.distributed.  sphere_quantile: the default halo covers
         this quantile of the near-face k-ball needs; the points beyond it keep coverage spheres (cut_spheres).
@@ -460,11 +462,15 @@ class SlabDenoiser:
         which prices the drift the first plan must cover; horizon: the iterations a plan is sized to cover (default
         check_every) -- the default halo of every later plan (rebalance, a coverage re-plan) prices each point's
         measured drift over that many iterations ahead (cut_spheres), so a run of `horizon` iterations needs no
-        coverage re-plan."""
+        coverage re-plan.  exact_nvt2: every rank's NVT2 runs the reference's arithmetic (edge vectors with LAPACK's
+        sign, pcd_denoiser_set_exact_nvt2; HIP engine only), also on the engines a re-plan rebuilds."""
         self.t = transport or LocalTransport()
         rank, world = self.t.rank, self.t.world
         # cell lattice of the ranks' snapshot indices: the fused loop's (pcd_native.fused_k_hint) unless given
         self.k_max, self.k_hint, self.seeding = k_max, k_hint or nat.fused_k_hint(k_max) or 32, seeding
+        self.exact_nvt2 = bool(exact_nvt2)
+        if self.exact_nvt2 and engine_factory is not None:
+            raise ValueError("exact_nvt2 is a switch of the HIP engine; an engine_factory builds its own engines")
         self.engine_factory = engine_factory
         self.native = (engine_factory is None) if native is None else bool(native)
         self.comm = self.t.native_comm() if self.native else None
@@ -600,7 +606,7 @@ class SlabDenoiser:
         self.owned_global = self.local[self.owned_local]
         if self.engine_factory is None:
             self.e = HipSlabEngine(s.pos, s.n, self.owned_local, self.k_max, s.lattice[0], s.lattice[1], s.coverage,
-                                   self.seeding, spheres=s.xr)
+                                   self.seeding, spheres=s.xr, exact_nvt2=self.exact_nvt2)
         else:
             self.e = self.engine_factory(s.pos, s.n, self.owned_local, self.k_max, s.coverage)
         if s.state is not None:
