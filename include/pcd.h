@@ -24,6 +24,9 @@
  *   pcd_nn_dist                     TorchUtils.Chamfer/Paper/HausdorffDistance Pointcloud/Modules/Utils.py:253-295
  *   pcd_mesh_update(_f32)           Mesh.updateVertices                        PatchGeneration/Modules/Mesh.py:377-418
  *   pcd_mesh_vta                    igl.vertex_triangle_adjacency (Mesh.__init__) PatchGeneration/Modules/Mesh.py:26
+ *   pcd_mesh_face_geometry / _face_scale / _nbr_count / _nbr_fill / _filter(_f32) / _denoise(_f32)
+ *                                   MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal and its helpers
+ *                                                       src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:47-244
  *   pcd_denoiser_*                  Processor.denoise / getMyFeatureDecomposition / denoiseUntilMinimumError loop body
  *                                                                              Pointcloud/Modules/Processor.py:110-185
  *   pcd_orient_normals_mst          GraphBuilder.flipNormals (MST + DFS, host) Pointcloud/Modules/GraphBuilder.py:129-209
@@ -169,6 +172,56 @@ int pcd_mesh_update_f32(float* v, int64_t nv, const int32_t* f, const float* fn,
  * f [nf][3] (int32 or int64 per f_bits) -> vf [3 nf] (the incident faces of each vertex in increasing face order) and
  * ni [nv + 1] offsets, int32 or int64 per out_bits.  PCD_ERR_ARG for a face index outside [0, nv).  Synchronises. */
 int pcd_mesh_vta(const void* f, int f_bits, int64_t nf, int64_t nv, void* vf, void* ni, int out_bits, void* stream);
+
+/* ------------------------------------------------------------------ guided bilateral normal filtering (mesh) */
+/* The reference's network-free mesh denoiser, src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:170-244.  fp64
+ * entries take plain rows and int64 indices; the _f32 entries take fp32 rows and int32 indices (float4 internally).
+ * vf / ni are the vertex->face CSR of pcd_mesh_vta.  Nothing here synchronises unless it says so. */
+/* MeshDenoisingBase::getFaceCentroid / getFaceArea / getFaceNormal (MeshDenoisingBase.cpp:24-65), normals oriented as
+ * Mesh.getFaceNormals (PatchGeneration/Modules/Mesh.py:110-114): centroid [nf][3] = ((p0+p1)+p2)/3, area [nf] =
+ * 0.5 |(p1-p0) x (p2-p1)|, normal [nf][3] = the unit cross product, zero for a face of zero area. */
+int pcd_mesh_face_geometry(const double* v, int64_t nv, const int64_t* f, int64_t nf, double* centroid, double* area,
+                           double* normal, void* stream);
+/* MeshNormalFiltering::getRadius / getSigmaS with multiple = 1 (MeshNormalFiltering.cpp:134-168): out2 (device) =
+ * {mean |c_f - c_g| over the ordered pairs of faces sharing an edge, the number of pairs}; {0, 0} without a pair.
+ * Deterministic fp64 reduction (block partials, then one block). */
+int pcd_mesh_face_scale(const double* centroid, const int64_t* f, int64_t nf, const int64_t* vf, const int64_t* ni,
+                        int64_t nv, double* out2, void* stream);
+/* MeshNormalFiltering::getRadiusBasedFaceNeighbor (MeshNormalFiltering.cpp:47-78; mode 0) or the vertex-based set of
+ * MeshDenoisingBase::getFaceNeighbor (MeshDenoisingBase.cpp:75-92; mode 1), centre included (include_central_face).
+ * Count: the search of face i runs inside rows[cap_off[i] .. cap_off[i+1]), which the caller sizes with an upper bound
+ * on the row (radius mode: the number of centroids within the radius; vertex mode: the degrees of its corners), and
+ * counts [nf] gets the row lengths.  PCD_ERR_ARG when a row does not fit (nothing is written past a segment).
+ * Synchronises.  Fill: with offsets [nf+1] = the exclusive prefix sums of counts, nbr_out [offsets[nf]] gets every
+ * row in ascending face index (the reference keeps its search order instead). */
+int pcd_mesh_nbr_count(const double* centroid, const int64_t* f, int64_t nf, const int64_t* vf, const int64_t* ni,
+                       int64_t nv, int mode, double radius, const int64_t* cap_off, int64_t* rows, int64_t* counts,
+                       void* stream);
+int pcd_mesh_nbr_fill(const int64_t* rows, const int64_t* cap_off, const int64_t* offsets, int64_t nf,
+                      int64_t* nbr_out, void* stream);
+/* One pass of the filter (MeshNormalFiltering.cpp:207-236) over the CSR (off, nbr): out_i = normalize(sum_j src_j A_j
+ * exp(-|c_i-c_j|^2 / 2 sigma_s^2) exp(-|g_i-g_j|^2 / 2 sigma_r^2)), sigma_s = multiple_sigma_s * scale[0] with scale
+ * the device output of pcd_mesh_face_scale.  A zero or non-finite sum keeps src_i; a neighbour of zero area weighs 0
+ * and is not read; a centre of zero area gets the zero normal.  _f32: total = off[nf]. */
+int pcd_mesh_filter(const double* centroid, const double* area, const double* guided, const double* src, int64_t nf,
+                    const int64_t* off, const int64_t* nbr, double sigma_r, double multiple_sigma_s,
+                    const double* scale, double* out, void* stream);
+int pcd_mesh_filter_f32(const float* centroid, const float* area, const float* guided, const float* src, int64_t nf,
+                        const int32_t* off, const int32_t* nbr, int64_t total, float sigma_r, float multiple_sigma_s,
+                        const double* scale, float* out, void* stream);
+/* MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal (MeshNormalFiltering.cpp:170-244): normal_iterations
+ * times {face geometry of the current mesh, sigma_s, one filter pass (src = guided in the first iteration, the current
+ * face normals afterwards), vertex_iterations sweeps of pcd_mesh_update}, in place on v; normals_out [nf][3] gets the
+ * last filtered normals.  guided null: the input mesh's own face normals guide (bilateral normal filtering).  The
+ * neighbourhoods (off, nbr) are the caller's, built once on the input mesh.  Vertices in no face keep their position.
+ * normal_iterations == 0 or an empty mesh: PCD_OK, nothing written. */
+int pcd_mesh_denoise(double* v, int64_t nv, const int64_t* f, int64_t nf, const int64_t* vf, const int64_t* ni,
+                     const int64_t* off, const int64_t* nbr, const double* guided, int normal_iterations,
+                     int vertex_iterations, double sigma_r, double multiple_sigma_s, double* normals_out, void* stream);
+int pcd_mesh_denoise_f32(float* v, int64_t nv, const int32_t* f, int64_t nf, const int32_t* vf, const int32_t* ni,
+                         const int32_t* off, const int32_t* nbr, int64_t total, const float* guided,
+                         int normal_iterations, int vertex_iterations, float sigma_r, float multiple_sigma_s,
+                         float* normals_out, void* stream);
 
 /* ------------------------------------------------------------------ fused denoise loop (H8, H13, H14) */
 typedef struct pcd_denoiser pcd_denoiser;

@@ -7,6 +7,11 @@ back into `self.v` in place, like the reference's `v += scaled_S`.
 The vertex-triangle adjacency is igl's format (VF = incident faces grouped by vertex in face order, NI = offsets),
 built on the device (pcd_mesh_vta: a stable radix sort of the corners by vertex) and kept there with the faces;
 `updateVertices(n, k, fp32=True)` runs the fp32 kernel (pcd_mesh_update_f32).
+
+`denoise(guided_normals=None, ...)` is the reference application's network-free mesh denoiser
+(src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:170-244): guided bilateral filtering of the face normals over
+radius-based face neighbourhoods, vertex_iterations sweeps of the update above after every pass, all on the device
+(pcd_mesh_denoise); `getFaceCentroids`, `getFaceAreas`, `getFaceNeighbourhoods` and `filterNormals` are its pieces.
 """
 from __future__ import annotations
 
@@ -111,3 +116,148 @@ class Mesh:
         else:
             _nat.mesh_update(vd, fd, nd, vfd, nid, k)
         v[...] = vd.cpu().numpy().astype(v.dtype, copy=False)
+
+    # ------------------------------------------------------------------------------ guided bilateral normal filtering
+    # The reference's network-free mesh denoiser (src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:170-244) on one
+    # device: face geometry, the mean centroid distance of edge-adjacent faces, the face neighbourhoods and the filter
+    # pass are HIP kernels (csrc/mesh.hip); the neighbourhoods and the geometry behind them are always fp64.
+    def _geometry(self):
+        """(v, f, vf, ni, centroid, area, normal) in fp64 / int64 on the device, for the current vertices."""
+        fd, vfd, nid = self._topology(False)
+        nv = len(self.getVertices())
+        if fd.numel() and (int(fd.min()) < 0 or int(fd.max()) >= nv):      # (a caller's vta is not checked elsewhere)
+            raise ValueError("Mesh: face index out of range [0, nv)")
+        vd = torch.as_tensor(np.ascontiguousarray(self.getVertices())).to(fd.device).to(torch.float64).contiguous()
+        return (vd, fd, vfd, nid) + _nat.mesh_face_geometry(vd, fd)
+
+    def getFaceCentroids(self):
+        """(p0 + p1 + p2) / 3 per face (MeshDenoisingBase::getFaceCentroid, MeshDenoisingBase.cpp:44-52), fp64."""
+        return self._geometry()[4].cpu().numpy()
+
+    def getFaceAreas(self):
+        """0.5 |(p1 − p0) × (p1 − p2)| per face (MeshDenoisingBase::getFaceArea, MeshDenoisingBase.cpp:24-42), fp64."""
+        return self._geometry()[5].cpu().numpy()
+
+    def getMeanCentroidDistance(self):
+        """Mean |c_f − c_g| over the ordered pairs of faces sharing an edge: getRadius / getSigmaS with multiple = 1
+        (MeshNormalFiltering.cpp:134-168)."""
+        _, fd, vfd, nid, c, _, _ = self._geometry()
+        return float(_nat.mesh_face_scale(c, fd, vfd, nid)[0])
+
+    def _neighbourhoods(self, mode, multiple_radius, radius, geometry=None):
+        """The CSR (offsets, faces) int64 on the device.  Cached with the topology (assigning f or vta drops it) and
+        with a host copy of the vertices it was measured on: radius-based rows depend on the centroids."""
+        if mode not in ("radius", "vertex"):
+            raise ValueError(f"Mesh: unknown neighbourhood mode {mode!r} (radius, vertex)")
+        if mode == "radius":
+            if radius is not None and not float(radius) >= 0:
+                raise ValueError("Mesh: radius must be >= 0")
+            if radius is None and not float(multiple_radius) > 0:
+                raise ValueError("Mesh: multiple_radius must be > 0")
+        key = ("nbr", mode) + ((None if radius is None else float(radius), float(multiple_radius))
+                               if mode == "radius" else ())
+        self._topology(False)                                   # (drops the cache when f was edited in place)
+        hit = self._topo.get(key)
+        if hit is not None and not (np.array_equal(hit[4], self.f) and
+                                    (mode != "radius" or np.array_equal(hit[0], self.getVertices()))):
+            hit = None
+        if hit is None:
+            _, fd, vfd, nid, c, _, _ = geometry if geometry is not None else self._geometry()
+            nf = fd.size(0)
+            if mode == "vertex":                                # bound: the degrees of the three corners
+                deg = nid[1:] - nid[:-1]
+                cap = deg[fd].sum(1) if nf else torch.zeros(0, dtype=torch.int64, device=fd.device)
+                r = 0.0
+            else:
+                r = float(radius) if radius is not None else \
+                    float(multiple_radius) * float(_nat.mesh_face_scale(c, fd, vfd, nid)[0])
+                if not np.isfinite(r):
+                    raise ValueError("Mesh: the neighbourhood radius is not finite")
+                # bound: the Euclidean ball count over the fp32 centroids, the radius widened by their rounding
+                if nf:
+                    c32 = c.to(torch.float32)
+                    r32 = np.nextafter(np.float32((r + 4e-7 * float(c.abs().max())) * (1 + 1e-6)), np.float32(np.inf))
+                    cap = _nat.Grid(c32).radius_counts(c32, torch.full((nf,), float(r32), device=c.device))
+                else:
+                    cap = torch.zeros(0, dtype=torch.int64, device=fd.device)
+            off, nbr = _nat.mesh_neighbourhoods(c, fd, vfd, nid, 0 if mode == "radius" else 1, r, cap.contiguous())
+            hit = (np.array(self.getVertices(), copy=True) if mode == "radius" else None, off, nbr, {},
+                   np.array(self.f, copy=True))
+            self._topo[key] = hit
+        return hit[1], hit[2], hit[3]
+
+    def getFaceNeighbourhoods(self, mode="radius", multiple_radius=2, radius=None):
+        """Face neighbourhoods as a CSR (offsets [nf+1], faces), rows in ascending face index, the face itself
+        included.  radius: faces reachable over vertex-sharing steps that stay within `radius` (default
+        multiple_radius x the mean centroid distance of edge-adjacent faces) of the centre's centroid
+        (MeshNormalFiltering::getRadiusBasedFaceNeighbor, MeshNormalFiltering.cpp:47-78) -- not the Euclidean ball;
+        vertex: faces sharing a vertex (MeshDenoisingBase.cpp:75-92)."""
+        off, nbr, _ = self._neighbourhoods(mode, multiple_radius, radius)
+        return off.cpu().numpy(), nbr.cpu().numpy()
+
+    @staticmethod
+    def _check_filter_args(nf, mode, sigma_r, multiple_sigma_s, **normals):
+        if mode not in ("radius", "vertex"):
+            raise ValueError(f"Mesh: unknown neighbourhood mode {mode!r} (radius, vertex)")
+        if not float(sigma_r) > 0 or not float(multiple_sigma_s) > 0:
+            raise ValueError("Mesh: sigma_r and multiple_sigma_s must be > 0")
+        for name, a in normals.items():
+            if a is not None and np.shape(a) != (nf, 3):
+                raise ValueError(f"Mesh: {name} must have one normal per face, shape ({nf}, 3), got {np.shape(a)}")
+
+    def filterNormals(self, guided=None, normals=None, sigma_r=0.3, multiple_sigma_s=1, mode="radius",
+                      multiple_radius=2, radius=None, fp32: bool = False):
+        """One pass of the guided bilateral filter (MeshNormalFiltering.cpp:207-236) over the current mesh; returns the
+        filtered unit normals [nf, 3].  guided: the guidance normals (None: the mesh's own face normals); normals: the
+        normals being averaged (None: the guidance, as in the reference's first iteration)."""
+        nf = len(self.f)
+        self._check_filter_args(nf, mode, sigma_r, multiple_sigma_s, guided=guided, normals=normals)
+        geo = self._geometry()
+        _, fd, vfd, nid, c, area, n = geo
+        off, nbr, extra = self._neighbourhoods(mode, multiple_radius, radius, geo)
+        scale = _nat.mesh_face_scale(c, fd, vfd, nid)
+        dt = torch.float32 if fp32 else torch.float64
+        dev = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(c.device).to(dt).contiguous()
+        g = n.to(dt) if guided is None else dev(guided)
+        src = g if normals is None else dev(normals)
+        if fp32:
+            off, nbr = self._csr32(off, nbr, extra)
+        out = _nat.mesh_filter(c.to(dt), area.to(dt), g, src, off, nbr, sigma_r, multiple_sigma_s, scale)
+        return out.cpu().numpy()
+
+    @staticmethod
+    def _csr32(off, nbr, extra):
+        if nbr.numel() >= 2 ** 31:
+            raise ValueError("Mesh: the fp32 path needs fewer than 2^31 neighbourhood entries")
+        if "i32" not in extra:
+            extra["i32"] = (off.to(torch.int32), nbr.to(torch.int32))
+        return extra["i32"]
+
+    def denoise(self, guided_normals=None, normal_iterations=12, vertex_iterations=16, sigma_r=0.3, multiple_radius=2,
+                multiple_sigma_s=1, mode="radius", fp32: bool = False):
+        """MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal (MeshNormalFiltering.cpp:170-244, defaults
+        :29-40): normal_iterations x {filter the face normals under the fixed guidance, vertex_iterations sweeps of
+        updateVertices}, in place on self.v; returns the last filtered normals.  guided_normals=None guides with the
+        input mesh's own face normals (bilateral normal filtering).  The neighbourhoods and the radius are those of
+        the input mesh.  Vertices in no face keep their position.  fp32=True runs the loop in fp32 (float4 rows, int32
+        topology); the neighbourhoods stay fp64."""
+        v = self.getVertices()
+        nf = len(self.f)
+        self._check_filter_args(nf, mode, sigma_r, multiple_sigma_s, guided_normals=guided_normals)
+        if int(normal_iterations) < 0 or int(vertex_iterations) < 0:
+            raise ValueError("Mesh: iteration counts must be >= 0")
+        geo = self._geometry()
+        off, nbr, extra = self._neighbourhoods(mode, multiple_radius, None, geo)
+        dt = torch.float32 if fp32 else torch.float64
+        g = None if guided_normals is None else \
+            torch.as_tensor(np.ascontiguousarray(guided_normals)).to(off.device).to(dt).contiguous()
+        if int(normal_iterations) == 0 or nf == 0:
+            return (geo[6].to(dt) if g is None else g).cpu().numpy()
+        fd, vfd, nid = self._topology(fp32)
+        if fp32:
+            off, nbr = self._csr32(off, nbr, extra)
+        vd = geo[0].to(dt).contiguous()
+        out = _nat.mesh_denoise(vd, fd, vfd, nid, off, nbr, g, normal_iterations, vertex_iterations, sigma_r,
+                                multiple_sigma_s)
+        v[...] = vd.cpu().numpy().astype(v.dtype, copy=False)
+        return out.cpu().numpy()

@@ -83,6 +83,19 @@ _SIGS = {
     "pcd_mesh_update_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                     c_void_p]),
     "pcd_mesh_vta": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    "pcd_mesh_face_geometry": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcd_mesh_face_scale": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pcd_mesh_nbr_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, ctypes.c_double,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcd_mesh_nbr_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pcd_mesh_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, ctypes.c_double,
+                                ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+    "pcd_mesh_filter_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "pcd_mesh_denoise": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
+    "pcd_mesh_denoise_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     "pcd_denoiser_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "pcd_denoiser_destroy": (c_int, [c_void_p]),
     "pcd_denoiser_load": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -771,6 +784,95 @@ def mesh_vta(f: torch.Tensor, nv: int, out_dtype=torch.int64):
     check(lib().pcd_mesh_vta(ptr(f), 32 if f.dtype == torch.int32 else 64, nf, int(nv), ptr(vf), ptr(ni),
                              32 if out_dtype == torch.int32 else 64, c_void_p(stream_ptr())), "pcd_mesh_vta")
     return vf, ni
+
+
+# guided bilateral normal filtering (MeshNormalFiltering.cpp:170-244); every tensor on the device, contiguous
+def _is(t, dtype, *shape):
+    return t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
+
+
+def mesh_face_geometry(v, f):
+    """(centroid [nf,3], area [nf], normal [nf,3]) of the faces f int64 [nf,3] over v float64 [nv,3]."""
+    nf = f.size(0)
+    assert _is(v, torch.float64, v.size(0), 3) and _is(f, torch.int64, nf, 3)
+    c = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
+    a = torch.empty(nf, dtype=torch.float64, device=v.device)
+    n = torch.empty((nf, 3), dtype=torch.float64, device=v.device)
+    check(lib().pcd_mesh_face_geometry(ptr(v), v.size(0), ptr(f), nf, ptr(c), ptr(a), ptr(n), c_void_p(stream_ptr())),
+          "pcd_mesh_face_geometry")
+    return c, a, n
+
+
+def mesh_face_scale(c, f, vf, ni):
+    """Device float64 [2]: the mean centroid distance of edge-adjacent faces, and the number of (ordered) pairs."""
+    nf, nv = f.size(0), ni.size(0) - 1
+    assert _is(c, torch.float64, nf, 3) and _is(f, torch.int64, nf, 3)
+    assert _is(vf, torch.int64, 3 * nf) and _is(ni, torch.int64, nv + 1)
+    out = torch.empty(2, dtype=torch.float64, device=c.device)
+    check(lib().pcd_mesh_face_scale(ptr(c), ptr(f), nf, ptr(vf), ptr(ni), nv, ptr(out), c_void_p(stream_ptr())),
+          "pcd_mesh_face_scale")
+    return out
+
+
+def mesh_neighbourhoods(c, f, vf, ni, mode, radius, cap):
+    """Face neighbourhoods as a CSR (offsets int64 [nf+1], faces int64, rows ascending): mode 0 radius-based, 1
+    vertex-based; cap int64 [nf] bounds every row's length from above (pcd_mesh_nbr_count / pcd_mesh_nbr_fill)."""
+    nf, nv = f.size(0), ni.size(0) - 1
+    assert _is(c, torch.float64, nf, 3) and _is(f, torch.int64, nf, 3) and _is(cap, torch.int64, nf)
+    assert _is(vf, torch.int64, 3 * nf) and _is(ni, torch.int64, nv + 1)
+    cap_off = torch.zeros(nf + 1, dtype=torch.int64, device=c.device)
+    torch.cumsum(cap, 0, out=cap_off[1:])
+    rows = torch.empty(int(cap_off[-1]) if nf else 0, dtype=torch.int64, device=c.device)
+    counts = torch.empty(nf, dtype=torch.int64, device=c.device)
+    check(lib().pcd_mesh_nbr_count(ptr(c), ptr(f), nf, ptr(vf), ptr(ni), nv, int(mode), float(radius), ptr(cap_off),
+                                   ptr(rows), ptr(counts), c_void_p(stream_ptr())), "pcd_mesh_nbr_count")
+    off = torch.zeros(nf + 1, dtype=torch.int64, device=c.device)
+    torch.cumsum(counts, 0, out=off[1:])
+    nbr = torch.empty(int(off[-1]) if nf else 0, dtype=torch.int64, device=c.device)
+    check(lib().pcd_mesh_nbr_fill(ptr(rows), ptr(cap_off), ptr(off), nf, ptr(nbr), c_void_p(stream_ptr())),
+          "pcd_mesh_nbr_fill")
+    return off, nbr
+
+
+def mesh_filter(c, area, guided, src, off, nbr, sigma_r, multiple_sigma_s, scale):
+    """One filter pass; the precision follows c (float64 rows with an int64 CSR, or float32 rows with an int32 one)."""
+    nf = c.size(0)
+    fp32 = c.dtype == torch.float32
+    dt, it = (torch.float32, torch.int32) if fp32 else (torch.float64, torch.int64)
+    assert _is(c, dt, nf, 3) and _is(area, dt, nf) and _is(guided, dt, nf, 3) and _is(src, dt, nf, 3)
+    assert _is(off, it, nf + 1) and nbr.dtype == it and nbr.is_contiguous() and _is(scale, torch.float64, 2)
+    out = torch.empty_like(src)
+    if fp32:
+        check(lib().pcd_mesh_filter_f32(ptr(c), ptr(area), ptr(guided), ptr(src), nf, ptr(off), ptr(nbr), nbr.numel(),
+                                        float(sigma_r), float(multiple_sigma_s), ptr(scale), ptr(out),
+                                        c_void_p(stream_ptr())), "pcd_mesh_filter_f32")
+    else:
+        check(lib().pcd_mesh_filter(ptr(c), ptr(area), ptr(guided), ptr(src), nf, ptr(off), ptr(nbr), float(sigma_r),
+                                    float(multiple_sigma_s), ptr(scale), ptr(out), c_void_p(stream_ptr())),
+              "pcd_mesh_filter")
+    return out
+
+
+def mesh_denoise(v, f, vf, ni, off, nbr, guided, normal_iterations, vertex_iterations, sigma_r, multiple_sigma_s):
+    """The whole loop in place on v (float64 + int64 topology, or float32 + int32); returns the last filtered normals.
+    guided None: the input mesh's own face normals."""
+    nf, nv = f.size(0), v.size(0)
+    fp32 = v.dtype == torch.float32
+    dt, it = (torch.float32, torch.int32) if fp32 else (torch.float64, torch.int64)
+    assert _is(v, dt, nv, 3) and _is(f, it, nf, 3) and _is(vf, it, 3 * nf) and _is(ni, it, nv + 1)
+    assert _is(off, it, nf + 1) and nbr.dtype == it and nbr.is_contiguous()
+    assert guided is None or _is(guided, dt, nf, 3)
+    out = torch.zeros((nf, 3), dtype=dt, device=v.device)
+    if fp32:
+        check(lib().pcd_mesh_denoise_f32(ptr(v), nv, ptr(f), nf, ptr(vf), ptr(ni), ptr(off), ptr(nbr), nbr.numel(),
+                                         ptr(guided), int(normal_iterations), int(vertex_iterations), float(sigma_r),
+                                         float(multiple_sigma_s), ptr(out), c_void_p(stream_ptr())),
+              "pcd_mesh_denoise_f32")
+    else:
+        check(lib().pcd_mesh_denoise(ptr(v), nv, ptr(f), nf, ptr(vf), ptr(ni), ptr(off), ptr(nbr), ptr(guided),
+                                     int(normal_iterations), int(vertex_iterations), float(sigma_r),
+                                     float(multiple_sigma_s), ptr(out), c_void_p(stream_ptr())), "pcd_mesh_denoise")
+    return out
 
 
 def list_cap(k: int) -> int:
