@@ -24,6 +24,8 @@
  *   pcd_nn_dist                     TorchUtils.Chamfer/Paper/HausdorffDistance Pointcloud/Modules/Utils.py:253-295
  *   pcd_mesh_update(_f32)           Mesh.updateVertices                        PatchGeneration/Modules/Mesh.py:377-418
  *   pcd_mesh_vta                    igl.vertex_triangle_adjacency (Mesh.__init__) PatchGeneration/Modules/Mesh.py:26
+ *   pcd_mesh_tta / pcd_patch_radius / _select_count / _select_fill / _inputs
+ *                                   PatchCollector.collectNetworkInput         PatchGeneration/Modules/PatchCollector.py:161-166
  *   pcd_mesh_face_geometry / _face_scale / _nbr_count / _nbr_fill / _filter(_f32) / _denoise(_f32)
  *                                   MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal and its helpers
  *                                                       src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:47-244
@@ -222,6 +224,54 @@ int pcd_mesh_denoise_f32(float* v, int64_t nv, const int32_t* f, int64_t nf, con
                          const int32_t* off, const int32_t* nbr, int64_t total, const float* guided,
                          int normal_iterations, int vertex_iterations, float sigma_r, float multiple_sigma_s,
                          float* normals_out, void* stream);
+
+/* ------------------------------------------------------------------ GCN network input (patches) */
+/* The reference's PatchCollector.collectNetworkInput per face: selectPaperPatch / createPatch / Patch.alignPatch /
+ * Patch.toGraph (PatchGeneration/Modules/Mesh.py:289-307, 473-506), RotationMatrix (RotationMatrix.py:9-35) and
+ * FileDataset.file2input (Network/DataUtils.py:41-70).  Everything is fp64 with int64 indices; vf / ni are the
+ * vertex->face CSR of pcd_mesh_vta, tt the edge adjacency of pcd_mesh_tta.  Nothing synchronises unless it says so. */
+/* igl.triangle_triangle_adjacency(f)[0]: tt [nf][3], slot e = the face across the edge (f[e], f[(e+1)%3]), -1 on a
+ * boundary edge and on an edge shared by more than two faces.  f int32 / int64 per f_bits, tt per out_bits.
+ * PCD_ERR_ARG for a face index outside [0, nv).  Synchronises. */
+int pcd_mesh_tta(const void* f, int f_bits, int64_t nf, int64_t nv, void* tt, int out_bits, void* stream);
+/* Per requested face faces[i] (Mesh.py:300-304): centre [n][3] = the mean of its corners, radius [n] =
+ * k sqrt(mean area of {face} U edge-neighbours U their edge-neighbours), absent neighbours skipped, the areas summed
+ * as numpy.sum does.  mean_area [n] (may be null) gets that mean: the reference takes the root with libm's
+ * pow(x, 0.5), which is not correctly rounded, so a caller that needs its last bit redoes k * pow(mean, 0.5) on the
+ * host (pcd_host_patch_radius); radius holds k * sqrt(mean), correctly rounded.  A face outside [0, nf) gets radius 0. */
+int pcd_patch_radius(const double* v, int64_t nv, const int64_t* f, int64_t nf, const int64_t* tt,
+                     const int64_t* faces, int64_t n, double k, double* centre, double* radius, double* mean_area,
+                     void* stream);
+/* Patch selection (Mesh.py:157-163, 242-251): patch i = every face with a vertex u, |v_u - centre_i| < radius_i
+ * (strict, rounded as numpy.linalg.norm rounds), rows ascending and duplicate-free.  g: a grid built over the nv
+ * vertices rounded to fp32; the kernels walk the cells that overlap the box of half-width radius_i + widen around the
+ * centre (widen: a bound on the fp32 rounding of the vertices and the centres, e.g. 4e-7 max|coordinate|) and put
+ * every row found there to the exact fp64 test on v.  Count: counts [n].  Fill: off [n+1] = the exclusive prefix sums
+ * of counts, patch_faces [capacity].  PCD_ERR_ARG when off[n] > capacity or a row does not have its counted length,
+ * and then nothing is written to patch_faces.  Fill synchronises. */
+int pcd_patch_select_count(const pcd_grid* g, double widen, const double* v, int64_t nv, const int64_t* f, int64_t nf,
+                           const int64_t* vf, const int64_t* ni, const double* centre, const double* radius, int64_t n,
+                           int64_t* counts, void* stream);
+int pcd_patch_select_fill(const pcd_grid* g, double widen, const double* v, int64_t nv, const int64_t* f, int64_t nf,
+                          const int64_t* vf, const int64_t* ni, const double* centre, const double* radius, int64_t n,
+                          const int64_t* off, int64_t capacity, int64_t* patch_faces, void* stream);
+/* radius[i] = k * pow(mean_area[i], 0.5) with the C library's pow on host arrays: the reference's `k * mean ** 0.5`
+ * on a numpy scalar, bit for bit (see pcd_patch_radius). */
+int pcd_host_patch_radius(const double* mean_area, int64_t n, double k, double* radius);
+/* Alignment and graph rows of the patches (off [n+1], patch_faces [total]) of faces [n], one workgroup per patch:
+ * centre on the mean of the patch's vertices, scale the farthest one to distance 1, T = sum_{j != centre} (A_j / max A)
+ * exp(-3 |c_j - c_i|) n'_j n'_j^T, rot [n][3][3] = its eigenvectors as rows in descending eigenvalue order (fp64 Jacobi),
+ * row 0 agreeing with the centre face's normal, row 1 with its largest component positive, row 2 = row 0 x row 1; then
+ * per patch the first 64 faces' rows of 20 columns {centroid 3, normal 3, area, edge-neighbours in the patch, corners
+ * 9, index columns 3}, zero-padded, of the rotated patch.  adjacency 0: the reference's index columns (the slot whose
+ * neighbour is local face 1, else 63); 1: the local edge-neighbours inside the window.  out: [n][64][20] (or
+ * [n][20][64] with channels_first) float64 / float32 per out_bits, the float32 being the float64 value rounded.
+ * centre_index [n]: the local index of the face in its own patch, -1 if absent; eig [n][3]: the eigenvalues,
+ * descending.  A face outside [0, nf) or an empty patch gives padding rows and the identity.  Bitwise repeatable. */
+int pcd_patch_inputs(const double* v, int64_t nv, const int64_t* f, int64_t nf, const int64_t* tt, const int64_t* vf,
+                     const int64_t* ni, const int64_t* faces, int64_t n, const int64_t* off, const int64_t* patch_faces,
+                     int64_t total, int adjacency, int out_bits, int channels_first, void* out, double* rot,
+                     int64_t* centre_index, double* eig, void* stream);
 
 /* ------------------------------------------------------------------ fused denoise loop (H8, H13, H14) */
 typedef struct pcd_denoiser pcd_denoiser;

@@ -60,6 +60,15 @@ class Mesh:
         self._vta = value
         self._topo = {}
 
+    @property
+    def f2f(self):
+        return self._f2f
+
+    @f2f.setter
+    def f2f(self, value):
+        self._f2f = value         # igl TT [nf, 3]; None: built on the device on first use (pcd_mesh_tta)
+        self._topo = {}
+
     @classmethod
     def readFile(cls, file_path: str) -> "Mesh":
         from Pointcloud.Modules.Object import read_obj_arrays
@@ -261,3 +270,109 @@ class Mesh:
                                 multiple_sigma_s)
         v[...] = vd.cpu().numpy().astype(v.dtype, copy=False)
         return out.cpu().numpy()
+
+    # ------------------------------------------------------------------------------------- patches (GCN network input)
+    # The selection half of the reference's patch pipeline (Mesh.py:141-163, 189-204, 242-251, 300-305) on the device:
+    # the edge adjacency (pcd_mesh_tta), the two-ring radius and the face centre (pcd_patch_radius), and the faces with
+    # a vertex strictly inside the ball as a CSR (pcd_patch_select_*).  PatchCollector builds the network rows on top.
+    def _adjacency(self):
+        """igl.triangle_triangle_adjacency(f)[0] as int64 [nf, 3] on the device: the caller's f2f when one was given,
+        else built on the device; cached with the topology."""
+        fd = self._topology(False)[0]
+        hit = self._topo.get("tta")
+        if hit is not None and not np.array_equal(hit[0], self.f):     # (f edited in place)
+            hit = None
+        if hit is None:
+            if self.f2f is not None:
+                tt = torch.as_tensor(np.ascontiguousarray(self.f2f)).to(fd.device).to(torch.int64).contiguous()
+                if tuple(tt.shape) != (fd.size(0), 3):
+                    raise ValueError(f"Mesh: f2f must have shape ({fd.size(0)}, 3), got {tuple(tt.shape)}")
+            else:
+                tt = _nat.mesh_tta(fd, len(self.getVertices()))
+            hit = (np.array(self.f, copy=True), tt)
+            self._topo["tta"] = hit
+        return hit[1]
+
+    def getTriangleTriangleAdjacency(self):
+        """igl.triangle_triangle_adjacency(f)[0]: [nf, 3], slot e = the face across the edge (f[e], f[(e+1)%3]), -1 on
+        a boundary edge and on an edge shared by more than two faces."""
+        if self.f2f is None:
+            self._f2f = self._adjacency().cpu().numpy()          # (the device copy it came from stays valid)
+        return self.f2f
+
+    def getNeighbourhood(self, face_index, ring):
+        """The faces within `ring` edge steps of face_index, ascending (Mesh.py:193-204); absent neighbours are
+        skipped, where the reference's -1 adds the last face of the mesh."""
+        if ring < 1:
+            return np.array([])
+        f2f = self.getTriangleTriangleAdjacency()
+        result = np.array([face_index], dtype=np.int64).reshape(-1)
+        for _ in range(ring):
+            nb = f2f[result].reshape(-1)
+            result = np.union1d(result, nb[nb >= 0])
+        return result
+
+    def getAreas(self, faces):
+        """0.5 |(v1 - v0) x (v2 - v0)| of the given faces (Mesh.py:144-150)."""
+        t = self.getVertices()[np.asarray(self.f)[np.asarray(faces).astype(int)]]
+        return 0.5 * np.linalg.norm(np.cross(t[..., 1, :] - t[..., 0, :], t[..., 2, :] - t[..., 0, :], axis=-1), axis=-1)
+
+    def _patch_state(self):
+        """What every patch query needs, on the device and cached against host copies of the vertices and faces:
+        (v fp64, f, vf, ni, tt, the grid over the fp32 vertices, max |coordinate|, the number of zero-area faces)."""
+        fd, vfd, nid = self._topology(False)
+        tt = self._adjacency()
+        hit = self._topo.get("patch")
+        if hit is not None and not (np.array_equal(hit[0], self.getVertices()) and np.array_equal(hit[1], self.f)):
+            hit = None
+        if hit is None:
+            vd, _, _, _, _, area, _ = self._geometry()
+            if not bool(torch.isfinite(vd).all()):
+                raise ValueError("Mesh: the vertices are not finite")
+            grid = _nat.Grid(vd.to(torch.float32)) if vd.size(0) else None
+            hit = (np.array(self.getVertices(), copy=True), np.array(self.f, copy=True), vd, grid,
+                   float(vd.abs().max()) if vd.numel() else 0.0, int((~(area > 0)).sum()))
+            self._topo["patch"] = hit
+        return (hit[2], fd, vfd, nid, tt) + hit[3:]
+
+    def _faces_arg(self, fis):
+        """The requested faces as int64 on the device, every one checked against [0, nf)."""
+        nf = len(self.f)
+        a = np.arange(nf, dtype=np.int64) if fis is None else np.asarray(fis)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("Mesh: face indices must be integers")
+        a = a.astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= nf):
+            raise ValueError(f"Mesh: face index out of range [0, {nf})")
+        return torch.as_tensor(a).to(_nat.device())
+
+    def _patch_balls(self, fis_d, k):
+        """(centre [n,3], r [n]) fp64 on the device for the faces fis_d (int64, on the device, in range)."""
+        vd, fd, _, _, tt = self._patch_state()[:5]
+        return _nat.patch_radius(vd, fd, tt, fis_d, k)
+
+    def _patches(self, fis_d, k, out=None, state=None):
+        """(centre, r, offsets, faces) of the patches of fis_d on the device.  The candidates of the exact fp64 test are
+        the rows of the grid over the fp32 vertices in the cells around the ball, each radius widened by the rounding of
+        the coordinates (as _neighbourhoods widens its own).  out: the int64
+        device buffer to fill instead of one of the exact size (ValueError, nothing written, if it is too small)."""
+        vd, fd, vfd, nid, tt, grid, vmax, _ = state if state is not None else self._patch_state()
+        centre, r = _nat.patch_radius(vd, fd, tt, fis_d, k)
+        n = fis_d.size(0)
+        if n == 0 or grid is None:
+            z = torch.zeros(n + 1, dtype=torch.int64, device=fd.device)
+            return centre, r, z, torch.zeros(0, dtype=torch.int64, device=fd.device)
+        if not bool(torch.isfinite(r).all()):
+            raise ValueError("Mesh: a patch radius is not finite")
+        off, faces = _nat.patch_select(grid, 4e-7 * vmax, vd, fd, vfd, nid, centre, r, out)
+        return centre, r, off, faces
+
+    def getPatchRadius(self, fis=None, k=4):
+        """r = k sqrt(mean area of the two-ring) per face of fis (Mesh.selectPaperPatch, Mesh.py:301-303), float64."""
+        return self._patch_balls(self._faces_arg(fis), k)[1].cpu().numpy()
+
+    def getPatchFaces(self, fis=None, k=4):
+        """The patches of the faces fis as a CSR (offsets [n+1], faces), rows ascending: every face with a vertex
+        strictly within r of the face's centre, over the whole mesh (Mesh.getFacesInRange, Mesh.py:157-163)."""
+        _, _, off, faces = self._patches(self._faces_arg(fis), k)
+        return off.cpu().numpy(), faces.cpu().numpy()

@@ -8,6 +8,7 @@ PyTorch is used for device memory, dtype/shape plumbing and the current stream o
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from ctypes import POINTER, c_double, c_float, c_int, c_int64, c_void_p
 
@@ -96,6 +97,17 @@ _SIGS = {
                                  c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
     "pcd_mesh_denoise_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int64, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "pcd_mesh_tta": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "pcd_patch_radius": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, ctypes.c_double,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcd_patch_select_count": (c_int, [c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pcd_patch_select_fill": (c_int, [c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pcd_host_patch_radius": (c_int, [c_void_p, c_int64, ctypes.c_double, c_void_p]),
+    "pcd_patch_inputs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
     "pcd_denoiser_create": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "pcd_denoiser_destroy": (c_int, [c_void_p]),
     "pcd_denoiser_load": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -873,6 +885,84 @@ def mesh_denoise(v, f, vf, ni, off, nbr, guided, normal_iterations, vertex_itera
                                      int(normal_iterations), int(vertex_iterations), float(sigma_r),
                                      float(multiple_sigma_s), ptr(out), c_void_p(stream_ptr())), "pcd_mesh_denoise")
     return out
+
+
+# the GCN network input (PatchCollector.collectNetworkInput); every tensor on the device, contiguous
+def mesh_tta(f: torch.Tensor, nv: int, out_dtype=torch.int64):
+    """igl.triangle_triangle_adjacency(f)[0] on the device: [nf, 3] in out_dtype (int32 / int64), -1 = no neighbour."""
+    f = on_device(f)
+    assert f.dtype in (torch.int32, torch.int64) and f.dim() == 2 and f.size(1) == 3
+    nf = f.size(0)
+    tt = torch.empty((nf, 3), dtype=out_dtype, device=f.device)
+    check(lib().pcd_mesh_tta(ptr(f), 32 if f.dtype == torch.int32 else 64, nf, int(nv), ptr(tt),
+                             32 if out_dtype == torch.int32 else 64, c_void_p(stream_ptr())), "pcd_mesh_tta")
+    return tt
+
+
+def patch_radius(v, f, tt, faces, k, libm_pow=True):
+    """(centre float64 [n,3], radius float64 [n]) of the patches of `faces` int64 [n] (pcd_patch_radius).
+    libm_pow: the reference writes r = k * mean ** 0.5 on a numpy scalar, which is libm's pow(mean, 0.5) and differs
+    from the correctly rounded root in the last bit now and then (2 of 640 faces of the shells fixture); to give the
+    reference's r bit for bit the device's mean areas (8 bytes per face) make a round trip through the same libm call.
+    False keeps the device's k * sqrt(mean) and the stage free of host work."""
+    nv, nf, n = v.size(0), f.size(0), faces.size(0)
+    assert _is(v, torch.float64, nv, 3) and _is(f, torch.int64, nf, 3) and _is(tt, torch.int64, nf, 3)
+    assert _is(faces, torch.int64, n)
+    centre = torch.empty((n, 3), dtype=torch.float64, device=v.device)
+    r = torch.empty(n, dtype=torch.float64, device=v.device)
+    mean = torch.empty(n, dtype=torch.float64, device=v.device) if libm_pow else None
+    check(lib().pcd_patch_radius(ptr(v), nv, ptr(f), nf, ptr(tt), ptr(faces), n, float(k), ptr(centre), ptr(r),
+                                 ptr(mean), c_void_p(stream_ptr())), "pcd_patch_radius")
+    if libm_pow and n:
+        host = mean.cpu()
+        rh = torch.empty_like(host)
+        check(lib().pcd_host_patch_radius(ptr(host), n, float(k), ptr(rh)), "pcd_host_patch_radius")
+        r = rh.to(v.device)
+    return centre, r
+
+
+def patch_select(grid, widen, v, f, vf, ni, centre, r, out=None):
+    """The patches as a CSR (offsets int64 [n+1], faces int64, rows ascending): every face with a vertex strictly
+    inside the ball (centre[i], r[i]).  grid: a Grid over v rounded to float32, widen: a bound on that rounding (added
+    to every radius when the cells to visit are chosen; membership is the exact float64 test).
+    out: the buffer to fill (its length is the capacity; ValueError, nothing written, when the patches do not fit);
+    None allocates the exact size (pcd_patch_select_count / pcd_patch_select_fill)."""
+    nv, nf, n = v.size(0), f.size(0), r.size(0)
+    assert _is(v, torch.float64, nv, 3) and _is(f, torch.int64, nf, 3)
+    assert _is(vf, torch.int64, 3 * nf) and _is(ni, torch.int64, nv + 1)
+    assert _is(centre, torch.float64, n, 3) and _is(r, torch.float64, n)
+    head = (grid.handle, float(widen), ptr(v), nv, ptr(f), nf, ptr(vf), ptr(ni), ptr(centre), ptr(r), n)
+    counts = torch.empty(n, dtype=torch.int64, device=v.device)
+    check(lib().pcd_patch_select_count(*head, ptr(counts), c_void_p(stream_ptr())), "pcd_patch_select_count")
+    off = torch.zeros(n + 1, dtype=torch.int64, device=v.device)
+    torch.cumsum(counts, 0, out=off[1:])
+    if out is None:
+        out = torch.empty(int(off[-1]) if n else 0, dtype=torch.int64, device=v.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.dim() == 1
+    check(lib().pcd_patch_select_fill(*head, ptr(off), out.numel(), ptr(out), c_void_p(stream_ptr())),
+          "pcd_patch_select_fill")
+    return off, out
+
+
+def patch_inputs(v, f, tt, vf, ni, faces, off, patch_faces, adjacency=False, dtype=torch.float64,
+                 channels_first=False):
+    """(inputs [n,64,20] (or [n,20,64]) in dtype, rotations float64 [n,3,3], centre_index int64 [n], eigenvalues
+    float64 [n,3]) of the patches (off, patch_faces) of `faces` (pcd_patch_inputs)."""
+    nv, nf, n = v.size(0), f.size(0), faces.size(0)
+    assert dtype in (torch.float64, torch.float32)
+    assert _is(v, torch.float64, nv, 3) and _is(f, torch.int64, nf, 3) and _is(tt, torch.int64, nf, 3)
+    assert _is(vf, torch.int64, 3 * nf) and _is(ni, torch.int64, nv + 1)
+    assert _is(faces, torch.int64, n) and _is(off, torch.int64, n + 1)
+    assert patch_faces.dtype == torch.int64 and patch_faces.is_contiguous() and patch_faces.dim() == 1
+    out = torch.empty((n, 20, 64) if channels_first else (n, 64, 20), dtype=dtype, device=v.device)
+    rot = torch.empty((n, 3, 3), dtype=torch.float64, device=v.device)
+    ci = torch.empty(n, dtype=torch.int64, device=v.device)
+    eig = torch.empty((n, 3), dtype=torch.float64, device=v.device)
+    check(lib().pcd_patch_inputs(ptr(v), nv, ptr(f), nf, ptr(tt), ptr(vf), ptr(ni), ptr(faces), n, ptr(off),
+                                 ptr(patch_faces), patch_faces.numel(), int(bool(adjacency)),
+                                 32 if dtype == torch.float32 else 64, int(bool(channels_first)), ptr(out), ptr(rot),
+                                 ptr(ci), ptr(eig), c_void_p(stream_ptr())), "pcd_patch_inputs")
+    return out, rot, ci, eig
 
 
 def list_cap(k: int) -> int:
