@@ -364,6 +364,7 @@ __global__ __launch_bounds__(BS) void k_patch_inputs(InputArgs a, OutT* __restri
     double ev[3] = {0, 0, 0};
     V3 mean{0, 0, 0};
     double scale = 1.0;
+    bool keep_centre = false;
     if (m > 0) {                                      // (uniform over the block)
         // --- the mean of the patch's vertices: a corner counts when its face is the first one of the vertex's
         //     incident faces (ascending) that lies in the patch
@@ -394,8 +395,9 @@ __global__ __launch_bounds__(BS) void k_patch_inputs(InputArgs a, OutT* __restri
         sn = block_sum<BS>(sn, red);
         if (sn > 0.0) mean = V3{sx / sn, sy / sn, sz / sn};
         // Patch.alignPatch :474-479: no translation when the centre is (numerically) the origin, no scaling when the
-        // size is (numerically) one -- numpy.allclose's 1e-8 + 1e-5 |b|
-        if (norm3(mean) <= 1e-8) mean = V3{0, 0, 0};
+        // size is (numerically) one -- numpy.allclose's 1e-8 + 1e-5 |b|.  An untranslated patch is still measured,
+        // resized and rotated about its true centre (Mesh.getPCSize, resize, rotate), which it then keeps.
+        keep_centre = norm3(mean) <= 1e-8;
         // --- the farthest vertex
         double d2 = 0.0;
         for (int64_t j = tid; j < m; j += BS) {
@@ -420,6 +422,7 @@ __global__ __launch_bounds__(BS) void k_patch_inputs(InputArgs a, OutT* __restri
             const int64_t g = row[j];
             V3 b[3];
             if (g < 0 || g >= a.nf || !corners(a.v, a.nv, a.f, g, b)) continue;
+            if (!(area_of(b) > 0.0)) continue;        // a zero-area face of the mesh adds nothing
             for (int c = 0; c < 3; ++c) b[c] = mul3(sub3(b[c], mean), scale);
             const V3 nj = normal_of(b);
             const double ar = area_of(b);
@@ -473,12 +476,15 @@ __global__ __launch_bounds__(BS) void k_patch_inputs(InputArgs a, OutT* __restri
         if (g >= 0 && g < a.nf) {
             V3 b[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
             const bool ok = corners(a.v, a.nv, a.f, g, b);
+            // a zero-area face of the mesh keeps a zero normal and area: the rotated corners' rounding gives neither
+            const bool flat = !(area_of(b) > 0.0);
             for (int c = 0; c < 3 && ok; ++c) {
                 const V3 s = mul3(sub3(b[c], mean), scale);
                 b[c] = V3{(R[0][0] * s.x + R[0][1] * s.y) + R[0][2] * s.z, (R[1][0] * s.x + R[1][1] * s.y) + R[1][2] * s.z,
                           (R[2][0] * s.x + R[2][1] * s.y) + R[2][2] * s.z};
+                if (keep_centre) b[c] = V3{b[c].x + mean.x, b[c].y + mean.y, b[c].z + mean.z};
             }
-            const V3 cen = centroid_of(b), nrm = normal_of(b);
+            const V3 cen = centroid_of(b), nrm = flat ? V3{0.0, 0.0, 0.0} : normal_of(b);
             int64_t loc[3];
             int found = 0;
             for (int e = 0; e < 3; ++e) {
@@ -488,7 +494,7 @@ __global__ __launch_bounds__(BS) void k_patch_inputs(InputArgs a, OutT* __restri
             }
             t[0] = cen.x; t[1] = cen.y; t[2] = cen.z;
             t[3] = nrm.x; t[4] = nrm.y; t[5] = nrm.z;
-            t[6] = area_of(b);
+            t[6] = flat ? 0.0 : area_of(b);
             t[7] = (double)found;
             for (int c = 0; c < 3; ++c) { t[8 + 3 * c] = b[c].x; t[9 + 3 * c] = b[c].y; t[10 + 3 * c] = b[c].z; }
             // file2input's three index columns

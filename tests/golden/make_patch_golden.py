@@ -1,4 +1,5 @@
-"""Generate tests/golden/patch_ellipsoid.npz and patch_shells*.npz by running the REFERENCE's patch pipeline.
+"""Generate tests/golden/patch_ellipsoid.npz, patch_shells*.npz and patch_align.npz by running the REFERENCE's patch
+pipeline.  `make_patch_golden.py NAME...` writes only the named ones (ellipsoid, shells, align); no name, all three.
 
 TEST INFRASTRUCTURE ONLY (build container, needs the reference checkout next to this repository's tests, as
 make_golden.py does).  The reference's PatchCollector.collectPatches, Patch.toGraph and FileDataset.file2input run
@@ -12,6 +13,9 @@ subdivided twice (162 vertices, 320 faces):
 Stored per fixture: v, f, the selection CSR and r for every face, the rotations, pi and relative eigen-gap for every
 face, the [64, 20] inputs of every third face plus every face whose centre lies beyond the window (input_faces), and
 the reference's seconds per patch.  The shells' inputs go to three files of their own so that no file passes 1 MiB.
+patch_align.npz holds the four boxes of patch_cases.BOXES (the two numpy.allclose branches of Patch.alignPatch), every
+array under "<variant>/<key>": all 12 inputs each, plus translated / scaled [12]: whether alignPatch called translate
+and resize on that patch.
 The generator asserts: selection margin min|d - r| / r >= 1e-8, relative gap >= 1e-5, no NaN.
 """
 import contextlib
@@ -26,6 +30,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+import patch_cases  # noqa: E402
 import refshim  # noqa: E402
 
 refshim.install()
@@ -107,11 +113,37 @@ def icosphere(levels):
     return np.array(v), np.array(f, dtype=np.int64)
 
 
-def run_reference(v, f, k=4):
+def run_reference(v, f, k=4, keep_all=False):
     mesh = Mesh(v.copy(), f.copy())
     mesh.gt = mesh.getFaceNormals()
-    log = {"sel": [], "eig": []}
+    log = {"sel": [], "eig": [], "branch": []}
     get_faces, get_rot = Mesh.getFacesInRange, Patch.getPaperRotationMatrix
+    get_align, get_translate, get_resize, get_rotate = Patch.alignPatch, Mesh.translate, Mesh.resize, Mesh.rotate
+    state = {"rec": None, "depth": 0}                    # alignPatch's own calls of translate / resize (depth 0)
+
+    def align(self):
+        state["rec"], state["depth"] = [False, False], 0
+        try:
+            return get_align(self)
+        finally:
+            log["branch"].append(tuple(state["rec"]))
+            state["rec"] = None
+
+    def translate(self, translation):
+        if state["rec"] is not None and state["depth"] == 0:
+            state["rec"][0] = True
+        return get_translate(self, translation)
+
+    def nested(inner, slot):
+        def call(self, arg):
+            if slot is not None and state["rec"] is not None and state["depth"] == 0:
+                state["rec"][slot] = True
+            state["depth"] += 1
+            try:
+                return inner(self, arg)
+            finally:
+                state["depth"] -= 1
+        return call
 
     def faces_in_range(self, center, rng):
         out = get_faces(self, center, rng)
@@ -125,6 +157,8 @@ def run_reference(v, f, k=4):
         return out
 
     Mesh.getFacesInRange, Patch.getPaperRotationMatrix = faces_in_range, rotation_matrix
+    Patch.alignPatch, Mesh.translate = align, translate
+    Mesh.resize, Mesh.rotate = nested(get_resize, 1), nested(get_rotate, None)
     try:
         pc = PatchCollector(mesh, k)
         t0 = time.perf_counter()
@@ -134,6 +168,8 @@ def run_reference(v, f, k=4):
         seconds = (time.perf_counter() - t0) / len(f)
     finally:
         Mesh.getFacesInRange, Patch.getPaperRotationMatrix = get_faces, get_rot
+        Patch.alignPatch, Mesh.translate, Mesh.resize, Mesh.rotate = get_align, get_translate, get_resize, get_rotate
+    assert len(log["branch"]) == len(f)
     rot = np.array([p[1].lastRotationApplied for p in patches])
     pi = np.array([int(np.asarray(p[1].pi).reshape(-1)[0]) for p in patches], dtype=np.int64)
     eig = np.array(log["eig"])
@@ -143,15 +179,29 @@ def run_reference(v, f, k=4):
     assert margin.min() >= 1e-8, margin.min()
     assert gap.min() >= 1e-5, gap.min()
     assert not np.isnan(inputs).any() and not np.isnan(rot).any()
-    keep = np.union1d(np.arange(0, len(f), 3), np.nonzero(pi >= 64)[0]).astype(np.int64)
+    keep = np.union1d(np.arange(0, len(f), 1 if keep_all else 3), np.nonzero(pi >= 64)[0]).astype(np.int64)
     return {"v": v, "f": f, "k": np.int64(k), "r": np.array([s[1] for s in log["sel"]]),
             "centre": np.array([s[0] for s in log["sel"]]),
             "off": np.concatenate([[0], np.cumsum([len(x) for x in rows])]).astype(np.int64),
             "faces": np.concatenate(rows), "rot": rot, "pi": pi, "eig": eig, "relgap": gap, "margin": margin,
-            "input_faces": keep, "inputs": inputs[keep], "seconds_per_patch": np.float64(seconds)}
+            "input_faces": keep, "inputs": inputs[keep], "seconds_per_patch": np.float64(seconds),
+            "translated": np.array([b[0] for b in log["branch"]]), "scaled": np.array([b[1] for b in log["branch"]])}
 
 
-def main():
+def write_align():
+    out = {}
+    for name in patch_cases.BOXES:
+        v, f = patch_cases.box_variant(name)
+        g = run_reference(v, f, keep_all=True)
+        g.pop("seconds_per_patch")
+        assert np.array_equal(np.diff(g["off"]), np.full(len(f), len(f))) and len(g["inputs"]) == len(f)
+        print(f"align/{name}: margin {g['margin'].min():.2e}, gap {g['relgap'].min():.2e}, "
+              f"translated {int(g['translated'].sum())}, scaled {int(g['scaled'].sum())} of {len(f)}")
+        out.update({f"{name}/{key}": val for key, val in g.items()})
+    np.savez_compressed(os.path.join(HERE, "patch_align.npz"), **out)
+
+
+def main(names=("ellipsoid", "shells", "align")):
     rng = np.random.default_rng(3)
     v0, f0 = icosphere(2)
     assert v0.shape == (162, 3) and f0.shape == (320, 3)
@@ -159,7 +209,10 @@ def main():
     sh = np.concatenate([v0, 1.12 * v0]) + rng.normal(0.0, 0.02, (2 * len(v0), 3))
     fsh = np.concatenate([f0, f0 + len(v0)])
     for name, v, f in (("ellipsoid", ell, f0), ("shells", sh, fsh)):
+        if name not in names:
+            continue
         g = run_reference(v, f)
+        del g["translated"], g["scaled"]
         sizes = np.diff(g["off"])
         print(f"{name}: {len(f)} faces, patches {sizes.min()}-{sizes.max()} faces, margin {g['margin'].min():.2e}, "
               f"gap {g['relgap'].min():.2e}, centres beyond the window {int((g['pi'] >= 64).sum())}, "
@@ -171,10 +224,12 @@ def main():
                 np.savez_compressed(os.path.join(HERE, f"patch_{name}_inputs_{part}.npz"), inputs=inputs[rows])
         else:
             np.savez_compressed(os.path.join(HERE, f"patch_{name}.npz"), inputs=inputs, **g)
+    if "align" in names:
+        write_align()
     for fn in os.listdir(HERE):
         if fn.startswith("patch_") and fn.endswith(".npz"):
             assert os.path.getsize(os.path.join(HERE, fn)) < 1 << 20, fn
 
 
 if __name__ == "__main__":
-    main()
+    main(tuple(sys.argv[1:]) or ("ellipsoid", "shells", "align"))
