@@ -29,6 +29,7 @@
  *   pcd_mesh_face_geometry / _face_scale / _nbr_count / _nbr_fill / _filter(_f32) / _denoise(_f32)
  *                                   MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal and its helpers
  *                                                       src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:47-244
+ *   pcd_dgcnn_*                     DGCNN.forward (eval)                       PatchGeneration/Modules/Network/GCNModel.py:121-215
  *   pcd_denoiser_*                  Processor.denoise / getMyFeatureDecomposition / denoiseUntilMinimumError loop body
  *                                                                              Pointcloud/Modules/Processor.py:110-185
  *   pcd_orient_normals_mst          GraphBuilder.flipNormals (MST + DFS, host) Pointcloud/Modules/GraphBuilder.py:129-209
@@ -492,6 +493,74 @@ int pcd_slab_iterate(pcd_denoiser* dn, pcd_comm* c, const pcd_denoise_params* p,
 int pcd_denoiser_set_readset(pcd_denoiser* dn, int on);
 /* since pcd_denoiser_set_routes: read-set iterations and the send / receive rows they moved, summed */
 int pcd_denoiser_readset_stats(const pcd_denoiser* dn, int64_t* iterations, int64_t* send_rows, int64_t* recv_rows);
+
+/* ------------------------------------------------------------------ DGCNN forward (inference, fp32) */
+/* DGCNN(k, init_dims = 17, emb_dims, dropout, output_channels) in eval(): three edge convolutions over the input's
+ * three index columns (17 -> 64 -> 64 -> 128), three over a k-nearest-neighbour graph rebuilt in feature space before
+ * each (128 -> 256 -> 256 -> 256), conv7 (1024 -> emb) over the concatenation, max and mean over the 64 nodes, and the
+ * head 2 emb -> 512 -> 256 -> 64 -> output_channels.  Batch norms use their running statistics (folded on the host in
+ * double with each layer's own eps, rounded once); dropout is the identity.  A patch's output depends on that patch
+ * only and is the same bits in any batch, at any place in it, in every run.  Neighbour ties go to the lower index. */
+typedef struct pcd_dgcnn pcd_dgcnn;
+typedef struct {
+    /* HOST or DEVICE pointers, row-major fp32.  conv 1-7: [rows][cols] = [out][2 in] (conv7: [emb][1024]);
+     * batch norms 1-10 (weight, bias, running mean, running var, eps, channels); linear 1-4: [out][in], bias [out]
+     * (linear1 has none: lin_b[0] must be null). */
+    const float* conv_w[7];
+    int32_t conv_rows[7], conv_cols[7];
+    const float* bn_weight[10];
+    const float* bn_bias[10];
+    const float* bn_mean[10];
+    const float* bn_var[10];
+    double bn_eps[10];
+    int32_t bn_len[10];
+    const float* lin_w[4];
+    const float* lin_b[4];
+    int32_t lin_rows[4], lin_cols[4];
+} pcd_dgcnn_weights;
+typedef struct {
+    /* optional DEVICE outputs of pcd_dgcnn_forward (null: not wanted) */
+    float* cat;          /* [b][1024][64] the six layer outputs, concatenated (conv7's input)        */
+    int32_t* lists;      /* [3][b][64][k] the neighbour lists of layers 4-6, ascending distance      */
+    float* pooled;       /* [b][2 emb]    max, then mean over the nodes                              */
+    float* h1;           /* [512][b], [256][b], [64][b]: the head's hidden layers, channels first    */
+    float* h2;
+    float* h3;
+} pcd_dgcnn_debug;
+/* Packs the weights on the device (copies; the caller's arrays are not kept).  PCD_ERR_ARG for init_dims != 17 (the
+ * forward slices rows 0:17), k outside [1, 64] and every shape that does not fit the layer table.  Synchronous. */
+int pcd_dgcnn_create(const pcd_dgcnn_weights* w, int k, int init_dims, int emb_dims, int output_channels,
+                     pcd_dgcnn** out);
+int pcd_dgcnn_destroy(pcd_dgcnn* m);
+/* bytes of caller-owned device scratch a forward of b patches needs (about 393 KB a patch) */
+int pcd_dgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes);
+/* inputs [b][20][64] fp32 (rows 0:17 features, 17:20 the index columns as floats, truncated as .long() does) ->
+ * out [b][output_channels].  An index outside [0, 63] or NaN is never used as an address: PCD_ERR_ARG naming the
+ * first such patch, nothing computed.  NaN / Inf features propagate to their own patch's output only.  A short
+ * or not 16-byte-aligned workspace is PCD_ERR_ARG and nothing is written.  Stream-ordered; synchronises `stream` once, after the index
+ * check.  Replaces DGCNN.forward (PatchGeneration/Modules/Network/GCNModel.py:170-215). */
+int pcd_dgcnn_forward(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                      int64_t workspace_bytes, const pcd_dgcnn_debug* debug, void* stream);
+/* The same without waiting for the device: a bad index column is not refused but recorded -- first_bad (DEVICE
+ * int32[1], set to PCD_DGCNN_NO_BAD_PATCH by the caller before the first chunk) takes the minimum of
+ * patch_base + patch over the bad patches, whose outputs are then computed from the clamped index 0 (no address is
+ * ever formed from a bad value).  The caller reads first_bad once, after its last chunk (predictNormals does).  The
+ * launches can be captured in a graph. */
+#define PCD_DGCNN_NO_BAD_PATCH 0x7f7f7f7f
+int pcd_dgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                               int64_t workspace_bytes, const pcd_dgcnn_debug* debug, int32_t* first_bad,
+                               int64_t patch_base, void* stream);
+/* Stages, for tests.  knn: x [b][channels][64] -> lists [b][64][k] (the k nearest rows in feature space, self
+ * included, ascending (d2, index)).  edgeconv: layer 1-6 of the model on x [b][Cin][64] with the given lists
+ * [b][64][list_len] (entries are taken mod 64) -> out [b][Cout][64]; synchronises `stream`. */
+int pcd_dgcnn_knn(const float* x, int64_t b, int channels, int k, int32_t* lists, void* stream);
+int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b, const int32_t* lists, int list_len,
+                       float* out, void* stream);
+/* The network's GEMM y = w . x on the exact-f32 MFMA: w [M][K]; nodes = 64: x [b][K][64] -> y [b][M][64]; nodes = 1:
+ * x [K][b] -> y [M][b].  epilogue 0: plain; 1: LeakyReLU_0.2(s[m] y + t[m]); 2 (nodes = 64): that, then max and mean
+ * over each patch's 64 columns -> y [b][2 M]; 3: s[m] y + t[m].  Synchronises `stream`. */
+int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64_t b, int nodes, int epilogue,
+                   const float* s, const float* t, float* y, void* stream);
 
 /* ------------------------------------------------------------------ normal orientation (host) */
 /* GraphBuilder.flipNormals: Kruskal MST on cost 1-|n_i·n_j| over the directed edge list (a[e] -> b[e],

@@ -258,8 +258,9 @@ class Mesh:
         geo = self._geometry()
         off, nbr, extra = self._neighbourhoods(mode, multiple_radius, None, geo)
         dt = torch.float32 if fp32 else torch.float64
-        g = None if guided_normals is None else \
-            torch.as_tensor(np.ascontiguousarray(guided_normals)).to(off.device).to(dt).contiguous()
+        if guided_normals is not None and not isinstance(guided_normals, torch.Tensor):
+            guided_normals = np.ascontiguousarray(guided_normals)     # (a device tensor stays on the device)
+        g = None if guided_normals is None else torch.as_tensor(guided_normals).to(off.device).to(dt).contiguous()
         if int(normal_iterations) == 0 or nf == 0:
             return (geo[6].to(dt) if g is None else g).cpu().numpy()
         fd, vfd, nid = self._topology(fp32)

@@ -7,8 +7,11 @@ turned into graph rows (Patch.toGraph) and padded / truncated to 64 rows with th
 pcd_patch_radius, the grid query + pcd_patch_select_*, pcd_patch_inputs (csrc/patch.hip).  `iterNetworkInput` yields the
 chunks as device tensors, so a large mesh never holds all of its 10 KB-per-face input at once.
 
-The file-system half of the reference class (savePatches, .mat files, directory scanning), the network and the
-training are not part of this package.  INTEGRATION.md lists where the output differs from the reference's on purpose
+`predictNormals(model)` takes those chunks through the network (Network/GCNModel.py, csrc/dgcnn.hip) and back to the
+mesh's frame, ready for Mesh.denoise(guided_normals=...).
+
+The file-system half of the reference class (savePatches, .mat files, directory scanning) and the training are not
+part of this package.  INTEGRATION.md lists where the output differs from the reference's on purpose
 (boundary faces, non-manifold edges, degenerate faces, the sign of the middle axis).
 """
 from __future__ import annotations
@@ -139,6 +142,36 @@ class PatchCollector:
         for s in range(0, fis_d.size(0), int(batch_faces)):
             yield self._batch(state, fis_d[s:s + int(batch_faces)].contiguous(), neighbours == "adjacency", dt,
                               bool(channels_first))
+
+    def predictNormals(self, model, batch_faces=4096, faces=None, neighbours="reference"):
+        """The network's normal of `faces` (None: every face) in the mesh's frame, ready for
+        Mesh.denoise(guided_normals=...): (normals float64 [n, 3] on the device, number of fallbacks).
+
+        Chunks of batch_faces patches go from iterNetworkInput (float32, channels first) through `model` (a
+        Network.GCNModel.DGCNN in eval(), on the device) with one workspace for all of them; each output o is taken
+        back with R^T o (PatchDataset.unalign's convention; the reference's NetworkController.py:257 computes R o) and
+        normalised.  A face keeps its own normal -- and is counted -- where its patch is empty, does not hold the
+        face (centre_index < 0), or the output is zero or not finite."""
+        fn = self.mesh._geometry()[6].to(torch.float64)
+        parts, fallbacks, ws, done = [], 0, None, 0
+        # a bad index column is recorded on the device and read once, after the last chunk: no chunk waits for it
+        first_bad = torch.full((1,), _nat.DGCNN_NO_BAD_PATCH, dtype=torch.int32, device=fn.device)
+        for b in self.iterNetworkInput(batch_faces, faces, neighbours, np.float32, channels_first=True):
+            if ws is None:                              # (the first chunk is the largest)
+                ws = model.native().workspace(b.inputs.size(0))
+            o = model(b.inputs, workspace=ws, first_bad=first_bad, patch_base=done).to(torch.float64)
+            done += b.inputs.size(0)
+            g = torch.einsum("nij,ni->nj", b.rotations.to(torch.float64), o)
+            norm = torch.linalg.vector_norm(g, dim=1, keepdim=True)
+            bad = (b.patch_size <= 0) | (b.centre_index < 0) | ~torch.isfinite(g).all(1) | ~(norm[:, 0] > 0)
+            parts.append(torch.where(bad[:, None], fn[b.faces], g / norm))
+            fallbacks += int(bad.sum())
+        if not parts:
+            return torch.zeros((0, 3), dtype=torch.float64, device=fn.device), 0
+        bad_patch = int(first_bad)
+        if bad_patch != _nat.DGCNN_NO_BAD_PATCH:
+            raise ValueError(f"PatchCollector: patch {bad_patch} of the request has an index column outside [0, 63]")
+        return torch.cat(parts), fallbacks
 
     def collectNetworkInput(self, max_batch_size, faces=None, neighbours="reference", dtype=np.float64):
         """PatchCollector.collectNetworkInput (PatchCollector.py:161-166) for `faces` (None: all): a PatchDataset of

@@ -1,0 +1,624 @@
+// The DGCNN forward pass (inference, fp32): GCNModel.py:121-215 of the reference as four kernels.
+//
+//   gemm_kernel    Y = W . X on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per output), 128 x 64
+//                  tiles, W shared by all patches, X the patches' columns.  Epilogues: plain store, per-row affine
+//                  (+ LeakyReLU 0.2), or affine + LeakyReLU + max / mean over the 64 columns of a patch (conv7:
+//                  [b, emb, 64] is never stored).
+//   index_kernel   the three index columns (floats) -> int32 lists, truncating as .long() does; a value outside
+//                  [0, 63] or a NaN is clamped to 0 and the lowest such patch raised in a device flag.
+//   knn_kernel     one workgroup per patch: 64 x 64 squared distances of the layer's input, the k smallest per row,
+//                  ascending, ties to the lower index (self included, as topk includes it).
+//   edge_kernel    out[c, i] = lrelu(max_j s_c (A[c, j] + B[c, i]) + t_c) over row i's list, where A = W_a X and
+//                  B = (W_b - W_a) X come from one GEMM: W [x_j - x_i ; x_i] = W_a x_j + (W_b - W_a) x_i.
+//
+// Every output element depends on its own patch only and is summed in a fixed order: a patch's output bits do not
+// depend on the batch, its place in it, or the run.  No float atomics.  The library's -ffp-contract=off stays; where a
+// fused multiply-add is meant the code says fmaf (or is the MFMA).
+#include <limits.h>
+#include <math.h>
+
+#include <vector>
+
+#include "pcd_host.h"
+
+using namespace pcd;
+
+namespace {
+
+constexpr int NODES = 64;            // rows of a patch
+constexpr int BM = 128, BN = 64, BK = 32;
+// LDS row strides (floats) of the W and X tiles: = 32 mod 64, so the two k rows an MFMA reads fall in different bank halves
+constexpr int LDA = 160, LDB = 96;
+constexpr int EPI_PLAIN = 0, EPI_AFFINE_LRELU = 1, EPI_POOL = 2, EPI_AFFINE = 3;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct GemmArgs {
+    const float* Wt;        // [K][M]: the weight, transposed (rows are contiguous in m)
+    const float* X;         // X(k, n) = X[(n / G) * xgs + k * xks + n % G]
+    float* Y;               // Y(m, n) = Y[(n / G) * ygs + m * yms + n % G]
+    const float* s;         // [M] (affine epilogues)
+    const float* t;
+    float* poolT;           // EPI_POOL: [2 M][b]  (max rows, then mean rows)
+    float* pool_dbg;        // EPI_POOL, nullable: [b][2 M]
+    int64_t N, G, xgs, xks, ygs, yms, b;
+    int M, K, epi;
+};
+
+__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
+// max that keeps a NaN (torch's max does)
+__device__ __forceinline__ float nanmax(float a, float b) { return (b > a || b != b) ? b : a; }
+
+__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
+    // K-tiles of W [BK][BM] and X [BK][BN]; afterwards the pooling epilogue's [BM][65] staging
+    __shared__ float lds[BM * 65];
+    static_assert(BM * 65 >= BK * (LDA + LDB), "the pooling staging must cover the k tiles");
+    float* As = lds;
+    float* Bs = lds + BK * LDA;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;   // a wave owns 64 x 32: two 32 x 32 accumulators sharing b
+    const int m0 = blockIdx.y * BM;
+    const int64_t n0 = (int64_t)blockIdx.x * BN;
+    // global -> LDS: this thread always moves column tid & 127 of the W tile (rows (tid >> 7) + 2 r) and column
+    // tid & 63 of the X tile (rows (tid >> 6) + 4 r)
+    const int wcol = tid & 127, wrow0 = tid >> 7, xcol = tid & 63, xrow0 = tid >> 6;
+    const int mg = m0 + wcol;
+    const int64_t ng = n0 + xcol;
+    const bool m_ok = mg < a.M, n_ok = ng < a.N;
+    const int64_t xoff = n_ok ? (ng / a.G) * a.xgs + ng % a.G : 0;
+    float wr[16], xr[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = k0 + wrow0 + 2 * r;
+            wr[r] = (m_ok && k < a.K) ? a.Wt[(int64_t)k * a.M + mg] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int k = k0 + xrow0 + 4 * r;
+            xr[r] = (n_ok && k < a.K) ? a.X[xoff + (int64_t)k * a.xks] : 0.f;
+        }
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+    fetch(0);
+    const int arow = lane >> 5, acol = lane & 31;
+    for (int k0 = 0; k0 < a.K; k0 += BK) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) As[(wrow0 + 2 * r) * LDA + wcol] = wr[r];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) Bs[(xrow0 + 4 * r) * LDB + xcol] = xr[r];
+        __syncthreads();
+        if (k0 + BK < a.K) fetch(k0 + BK);
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            const float a0 = As[(kk + arow) * LDA + wm + acol];
+            const float a1 = As[(kk + arow) * LDA + wm + 32 + acol];
+            const float bv = Bs[(kk + arow) * LDB + wn + acol];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc[1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // C layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int cn = wn + acol;
+    const int64_t n = n0 + cn;
+    float* Ps = lds;                                   // EPI_POOL: [BM][65] staging (every wave is past the k loop)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rm = wm + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * arow;
+            const int m = m0 + rm;
+            float v = acc[h][r];
+            if (a.epi != EPI_PLAIN && m < a.M) {
+                v = fmaf(a.s[m], v, a.t[m]);
+                if (a.epi != EPI_AFFINE) v = lrelu(v);
+            }
+            if (a.epi == EPI_POOL) {
+                Ps[rm * 65 + cn] = v;
+            } else if (m < a.M && n < a.N) {
+                a.Y[(n / a.G) * a.ygs + (int64_t)m * a.yms + n % a.G] = v;
+            }
+        }
+    }
+    if (a.epi != EPI_POOL) return;
+    __syncthreads();
+    // one row per 4 threads, 16 columns each in column order, then ((q0 + q1) + (q2 + q3)): a fixed-order sum
+    const int q = tid & 3;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int pr = half * 64 + (tid >> 2);
+        float sum = 0.f, mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float v = Ps[pr * 65 + q * 16 + c];
+            sum += v;
+            mx = nanmax(mx, v);
+        }
+        sum += __shfl_xor(sum, 1);
+        mx = nanmax(mx, __shfl_xor(mx, 1));
+        sum += __shfl_xor(sum, 2);
+        mx = nanmax(mx, __shfl_xor(mx, 2));
+        const int m = m0 + pr;
+        if (q == 0 && m < a.M) {
+            const int64_t p = blockIdx.x;              // G == BN: one patch per column tile
+            const float mean = sum * (1.f / NODES);
+            a.poolT[(int64_t)m * a.b + p] = mx;
+            a.poolT[((int64_t)a.M + m) * a.b + p] = mean;
+            if (a.pool_dbg) {
+                a.pool_dbg[p * 2 * a.M + m] = mx;
+                a.pool_dbg[p * 2 * a.M + a.M + m] = mean;
+            }
+        }
+    }
+}
+
+__global__ void transpose_kernel(const float* W, int M, int K, float* Wt) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)M * K) return;
+    const int k = (int)(e / M), m = (int)(e % M);
+    Wt[e] = W[(int64_t)m * K + k];
+}
+
+// inputs [b][20][64] -> lists [b][64][3]; flag: lowest patch with an index column outside [0, 63] (or NaN)
+__global__ void index_kernel(const float* inputs, int64_t b, int32_t* lists, int* flag, int patch_base) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= b * NODES * 3) return;
+    const int64_t p = e / (NODES * 3);
+    const int rem = (int)(e % (NODES * 3));
+    const int c = rem / NODES, i = rem % NODES;
+    const float f = inputs[p * (20 * NODES) + (17 + c) * NODES + i];
+    const bool ok = f > -1.0f && f < 64.0f;            // (int)f in [0, 63]; a NaN fails both
+    lists[(p * NODES + i) * 3 + c] = ok ? (int)f : 0;
+    if (!ok) atomicMin(flag, patch_base + (int)p);
+}
+
+// x [b] patches of [C][64] (patch stride xgs floats) -> lists [b][64][k]
+__global__ __launch_bounds__(256) void knn_kernel(const float* x, int64_t xgs, int C, int k, int32_t* lists) {
+    __shared__ float Xs[64 * NODES];
+    __shared__ float Ds[NODES * 65];
+    const int tid = threadIdx.x, i = tid & 63, j0 = (tid >> 6) * 16;
+    const float* xp = x + (int64_t)blockIdx.x * xgs;
+    float acc[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) acc[jj] = 0.f;
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int cc = min(64, C - c0);
+        for (int e = tid; e < cc * NODES; e += 256) Xs[e] = xp[(int64_t)c0 * NODES + e];
+        __syncthreads();
+        for (int c = 0; c < cc; ++c) {
+            const float xi = Xs[c * NODES + i];
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) {
+                const float d = xi - Xs[c * NODES + j0 + jj];
+                acc[jj] = fmaf(d, d, acc[jj]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) Ds[i * 65 + j0 + jj] = acc[jj] != acc[jj] ? INFINITY : acc[jj];   // NaN sorts last
+    __syncthreads();
+    // (distance, index) is a strict total order, so the ranks of a row are a permutation of 0..63
+    int rank[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) rank[jj] = 0;
+    for (int j = 0; j < NODES; ++j) {
+        const float d = Ds[i * 65 + j];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) {
+            const float dj = Ds[i * 65 + j0 + jj];
+            rank[jj] += (d < dj || (d == dj && j < j0 + jj)) ? 1 : 0;
+        }
+    }
+    int32_t* out = lists + ((int64_t)blockIdx.x * NODES + i) * k;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj)
+        if (rank[jj] < k) out[rank[jj]] = j0 + jj;
+}
+
+// P [b][2 Cout][64] (A rows, then B rows) -> out[c][i] = lrelu(max_j fmaf(s_c, A[c][j] + B[c][i], t_c))
+__global__ __launch_bounds__(256) void edge_kernel(const float* P, int Cout, const int32_t* lists, int kk, const float* s,
+                                                   const float* t, float* out, int64_t ogs) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= Cout) return;
+    const int64_t p = blockIdx.x;
+    const float* A = P + (p * 2 * Cout + c) * NODES;
+    const float Bi = A[(int64_t)Cout * NODES + i];
+    const float sc = s[c], tc = t[c];
+    const int32_t* row = lists + (p * NODES + i) * kk;
+    float m = -INFINITY;
+    for (int j = 0; j < kk; ++j) {
+        const int nb = row[j] & 63;                    // (lists are made by index_kernel / knn_kernel: in range)
+        m = nanmax(m, fmaf(sc, A[nb] + Bi, tc));
+    }
+    out[p * ogs + (int64_t)c * NODES + i] = lrelu(m);
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+const int kCin[6] = {17, 64, 64, 128, 256, 256};
+const int kCout[6] = {64, 64, 128, 256, 256, 256};
+const int kCatOff[6] = {0, 64, 128, 256, 512, 768};   // the layer's slice of the [1024][64] concatenation
+const int kHead[3] = {512, 256, 64};
+
+int launch_gemm(const GemmArgs& a, hipStream_t st) {
+    if (a.N <= 0 || a.M <= 0) return PCD_OK;
+    dim3 grid((unsigned)cdiv(a.N, BN), (unsigned)cdiv(a.M, BM));
+    hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, st, a);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+// conv form: X [b][K][64] (patch stride xgs) -> Y [b][M][64] (patch stride ygs)
+GemmArgs conv_args(const float* Wt, int M, int K, const float* X, int64_t xgs, float* Y, int64_t ygs, int64_t b) {
+    GemmArgs a{};
+    a.Wt = Wt; a.X = X; a.Y = Y; a.M = M; a.K = K; a.b = b;
+    a.N = b * NODES; a.G = NODES; a.xgs = xgs; a.xks = NODES; a.ygs = ygs; a.yms = NODES;
+    a.epi = EPI_PLAIN;
+    return a;
+}
+// head form: X [K][b] -> Y [M][b]
+GemmArgs head_args(const float* Wt, int M, int K, const float* X, float* Y, int64_t b) {
+    GemmArgs a{};
+    a.Wt = Wt; a.X = X; a.Y = Y; a.M = M; a.K = K; a.b = b;
+    a.N = b; a.G = b; a.xgs = 0; a.xks = b; a.ygs = 0; a.yms = b;
+    a.epi = EPI_PLAIN;
+    return a;
+}
+
+}  // namespace
+
+struct pcd_dgcnn {
+    int k = 0, emb = 0, out_ch = 0;
+    float* dev = nullptr;          // every packed weight in one allocation
+    const float* wt[11] = {};      // transposed: 6 edge layers [Cin][2 Cout], conv7 [1024][emb], linear1-4
+    const float* s[11] = {};       // folded batch norms 1-10 (s, t); [10]: linear4 (1, bias)
+    const float* t[11] = {};
+};
+
+namespace {
+
+struct Workspace {
+    int64_t cat, P, idx3, knn, pooled, h1, h2, h3, flag, total;   // byte offsets
+};
+Workspace layout(const pcd_dgcnn* m, int64_t b) {
+    Workspace w{};
+    int64_t o = 0;
+    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    w.cat = take(b * 1024 * NODES * 4);
+    w.P = take(b * 512 * NODES * 4);
+    w.idx3 = take(b * NODES * 3 * 4);
+    w.knn = take(3 * b * NODES * m->k * 4);
+    w.pooled = take(2 * (int64_t)m->emb * b * 4);
+    w.h1 = take(512 * b * 4);
+    w.h2 = take(256 * b * 4);
+    w.h3 = take(64 * b * 4);
+    w.flag = take(4);
+    w.total = o;
+    return w;
+}
+
+int run_edge(const pcd_dgcnn* m, int layer, const float* X, int64_t xgs, const int32_t* lists, int kk, float* P,
+             float* out, int64_t ogs, int64_t b, hipStream_t st) {
+    const int Cin = kCin[layer], Cout = kCout[layer];
+    const int rc = launch_gemm(conv_args(m->wt[layer], 2 * Cout, Cin, X, xgs, P, (int64_t)2 * Cout * NODES, b), st);
+    if (rc != PCD_OK) return rc;
+    hipLaunchKernelGGL(edge_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
+                       m->s[layer], m->t[layer], out, ogs);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+int run_knn(const float* x, int64_t xgs, int C, int k, int32_t* lists, int64_t b, hipStream_t st) {
+    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)b), dim3(256), 0, st, x, xgs, C, k, lists);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
+constexpr int64_t kMaxBatch = 1 << 20;   // 2^31 / (64 x 20) patches and more would pass int32 in the index flag
+
+}  // namespace
+
+extern "C" {
+
+int pcd_dgcnn_create(const pcd_dgcnn_weights* w, int k, int init_dims, int emb_dims, int output_channels,
+                     pcd_dgcnn** out) {
+    PCD_CHECK_ARG(out != nullptr, "out is null");
+    *out = nullptr;
+    PCD_CHECK_ARG(w != nullptr, "weights is null");
+    PCD_CHECK_ARG(init_dims == 17, "init_dims must be 17 (the network's forward slices rows 0:17 of its input)");
+    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
+    PCD_CHECK_ARG(emb_dims >= 1 && emb_dims <= (1 << 16), "emb_dims must be in [1, 65536]");
+    PCD_CHECK_ARG(output_channels >= 1 && output_channels <= 4096, "output_channels must be in [1, 4096]");
+    // the shapes of the layer table
+    int cr[7], cc[7], bl[10], lr[4], lc[4];
+    for (int l = 0; l < 6; ++l) { cr[l] = kCout[l]; cc[l] = 2 * kCin[l]; bl[l] = kCout[l]; }
+    cr[6] = emb_dims; cc[6] = 1024; bl[6] = emb_dims;
+    lr[0] = 512; lc[0] = 2 * emb_dims; lr[1] = 256; lc[1] = 512; lr[2] = 64; lc[2] = 256;
+    lr[3] = output_channels; lc[3] = 64;
+    bl[7] = 512; bl[8] = 256; bl[9] = 64;
+    for (int l = 0; l < 7; ++l) {
+        PCD_CHECK_ARG(w->conv_w[l] != nullptr, "conv" + std::to_string(l + 1) + " weight is null");
+        PCD_CHECK_ARG(w->conv_rows[l] == cr[l] && w->conv_cols[l] == cc[l],
+                      "conv" + std::to_string(l + 1) + " weight must be [" + std::to_string(cr[l]) + ", " +
+                          std::to_string(cc[l]) + "], got [" + std::to_string(w->conv_rows[l]) + ", " +
+                          std::to_string(w->conv_cols[l]) + "]");
+    }
+    for (int l = 0; l < 10; ++l) {
+        PCD_CHECK_ARG(w->bn_weight[l] && w->bn_bias[l] && w->bn_mean[l] && w->bn_var[l],
+                      "bn" + std::to_string(l + 1) + " has a null pointer");
+        PCD_CHECK_ARG(w->bn_len[l] == bl[l], "bn" + std::to_string(l + 1) + " must have " + std::to_string(bl[l]) +
+                                                 " channels, got " + std::to_string(w->bn_len[l]));
+        PCD_CHECK_ARG(w->bn_eps[l] >= 0.0 && w->bn_eps[l] == w->bn_eps[l], "bn" + std::to_string(l + 1) + " eps is invalid");
+    }
+    for (int l = 0; l < 4; ++l) {
+        PCD_CHECK_ARG(w->lin_w[l] != nullptr, "linear" + std::to_string(l + 1) + " weight is null");
+        PCD_CHECK_ARG(w->lin_rows[l] == lr[l] && w->lin_cols[l] == lc[l],
+                      "linear" + std::to_string(l + 1) + " weight must be [" + std::to_string(lr[l]) + ", " +
+                          std::to_string(lc[l]) + "], got [" + std::to_string(w->lin_rows[l]) + ", " +
+                          std::to_string(w->lin_cols[l]) + "]");
+        PCD_CHECK_ARG((w->lin_b[l] != nullptr) == (l > 0),
+                      l == 0 ? std::string("linear1 has no bias") : "linear" + std::to_string(l + 1) + " bias is null");
+    }
+    // everything to the host (the pointers may be host or device memory), folded in double, rounded once
+    auto pull = [](const float* src, int64_t n, std::vector<float>& dst) {
+        dst.resize(n);
+        return hipMemcpy(dst.data(), src, n * sizeof(float), hipMemcpyDefault);
+    };
+    std::vector<float> packed;
+    int64_t wt_off[11], s_off[11], t_off[11];
+    std::vector<float> W, g, be, mu, var, bias;
+    auto fold = [&](int l, const std::vector<float>* lin_bias) {     // batch norm l -> (s, t)
+        const int n = bl[l];
+        s_off[l] = (int64_t)packed.size();
+        for (int c = 0; c < n; ++c) packed.push_back((float)((double)g[c] / sqrt((double)var[c] + w->bn_eps[l])));
+        t_off[l] = (int64_t)packed.size();
+        for (int c = 0; c < n; ++c) {
+            const double sc = (double)g[c] / sqrt((double)var[c] + w->bn_eps[l]);
+            const double shift = (lin_bias ? (double)(*lin_bias)[c] : 0.0) - (double)mu[c];
+            packed.push_back((float)((double)be[c] + sc * shift));
+        }
+    };
+    auto pull_bn = [&](int l) -> hipError_t {
+        hipError_t e = pull(w->bn_weight[l], bl[l], g);
+        if (e == hipSuccess) e = pull(w->bn_bias[l], bl[l], be);
+        if (e == hipSuccess) e = pull(w->bn_mean[l], bl[l], mu);
+        if (e == hipSuccess) e = pull(w->bn_var[l], bl[l], var);
+        return e;
+    };
+    for (int l = 0; l < 7; ++l) {
+        PCD_HIP(pull(w->conv_w[l], (int64_t)cr[l] * cc[l], W));
+        PCD_HIP(pull_bn(l));
+        wt_off[l] = (int64_t)packed.size();
+        if (l < 6) {                                   // [W_a ; W_b - W_a], transposed to [Cin][2 Cout]
+            const int Cin = kCin[l], Cout = kCout[l];
+            for (int kq = 0; kq < Cin; ++kq) {
+                for (int c = 0; c < Cout; ++c) packed.push_back(W[(int64_t)c * 2 * Cin + kq]);
+                for (int c = 0; c < Cout; ++c)
+                    packed.push_back((float)((double)W[(int64_t)c * 2 * Cin + Cin + kq] - (double)W[(int64_t)c * 2 * Cin + kq]));
+            }
+        } else {
+            for (int kq = 0; kq < 1024; ++kq)
+                for (int c = 0; c < emb_dims; ++c) packed.push_back(W[(int64_t)c * 1024 + kq]);
+        }
+        fold(l, nullptr);
+    }
+    for (int l = 0; l < 4; ++l) {
+        PCD_HIP(pull(w->lin_w[l], (int64_t)lr[l] * lc[l], W));
+        if (l > 0) PCD_HIP(pull(w->lin_b[l], lr[l], bias));
+        wt_off[7 + l] = (int64_t)packed.size();
+        for (int kq = 0; kq < lc[l]; ++kq)
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(W[(int64_t)c * lc[l] + kq]);
+        if (l < 3) {
+            PCD_HIP(pull_bn(7 + l));
+            fold(7 + l, l > 0 ? &bias : nullptr);
+        } else {
+            s_off[10] = (int64_t)packed.size();
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(1.f);
+            t_off[10] = (int64_t)packed.size();
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(bias[c]);
+        }
+    }
+    pcd_dgcnn* m = new pcd_dgcnn();
+    m->k = k; m->emb = emb_dims; m->out_ch = output_channels;
+    hipError_t e = hipMalloc((void**)&m->dev, packed.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(m->dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (m->dev) (void)hipFree(m->dev);
+        delete m;
+        return fail(e == hipErrorOutOfMemory ? PCD_ERR_OOM : PCD_ERR_HIP,
+                    std::string("pcd_dgcnn_create: ") + hipGetErrorString(e));
+    }
+    for (int l = 0; l < 11; ++l) {
+        m->wt[l] = m->dev + wt_off[l];
+        m->s[l] = m->dev + s_off[l];
+        m->t[l] = m->dev + t_off[l];
+    }
+    *out = m;
+    return PCD_OK;
+}
+
+int pcd_dgcnn_destroy(pcd_dgcnn* m) {
+    if (!m) return PCD_OK;
+    if (m->dev) (void)hipFree(m->dev);
+    delete m;
+    return PCD_OK;
+}
+
+int pcd_dgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes) {
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    *bytes = layout(m, b).total;
+    return PCD_OK;
+}
+
+// first_bad null: the index flag lives in the workspace, is read after the index kernel (one stream synchronise) and
+// a bad index column refuses the call.  Otherwise the caller's device flag takes atomicMin(patch_base + patch), the
+// clamped indices are used and nothing waits for the device.
+static int forward_impl(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                        int64_t workspace_bytes, const pcd_dgcnn_debug* debug, int32_t* first_bad, int64_t patch_base,
+                        void* stream) {
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(inputs != nullptr && out != nullptr, "inputs / out is null");
+    const Workspace w = layout(m, b);
+    PCD_CHECK_ARG(workspace != nullptr && workspace_bytes >= w.total,
+                  "workspace of " + std::to_string(workspace_bytes) + " bytes is shorter than the " +
+                      std::to_string(w.total) + " that pcd_dgcnn_workspace_bytes asks for");
+    PCD_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+    PCD_CHECK_ARG(patch_base >= 0 && patch_base + b < kNoBadPatch, "patch_base + b must be in [0, 0x7f7f7f7f)");
+    hipStream_t st = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* cat = reinterpret_cast<float*>(ws + w.cat);
+    float* P = reinterpret_cast<float*>(ws + w.P);
+    int32_t* idx3 = reinterpret_cast<int32_t*>(ws + w.idx3);
+    int32_t* knn = reinterpret_cast<int32_t*>(ws + w.knn);
+    float* pooled = reinterpret_cast<float*>(ws + w.pooled);
+    float* h1 = reinterpret_cast<float*>(ws + w.h1);
+    float* h2 = reinterpret_cast<float*>(ws + w.h2);
+    float* h3 = reinterpret_cast<float*>(ws + w.h3);
+    int* flag = reinterpret_cast<int*>(ws + w.flag);
+    const int64_t cgs = 1024 * NODES;
+
+    // the index columns first: a bad one ends the call before anything is computed from it (or, deferred, is
+    // recorded in the caller's flag while the clamped index is used)
+    if (first_bad) {
+        hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, idx3,
+                           first_bad, (int)patch_base);
+        PCD_LAUNCH_CHECK();
+    } else {
+        int bad = kNoBadPatch;
+        PCD_HIP(hipMemsetAsync(flag, 0x7f, sizeof(int), st));
+        hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, idx3, flag, 0);
+        PCD_LAUNCH_CHECK();
+        PCD_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        PCD_HIP(hipStreamSynchronize(st));
+        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
+                                          " has an index column (rows 17:20) outside [0, 63] or NaN; no output written");
+    }
+
+    int rc;
+    for (int l = 0; l < 6; ++l) {
+        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
+        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
+        const int32_t* lists = idx3;
+        int kk = 3;
+        if (l >= 3) {
+            int32_t* mine = knn + (int64_t)(l - 3) * b * NODES * m->k;
+            if ((rc = run_knn(X, xgs, kCin[l], m->k, mine, b, st)) != PCD_OK) return rc;
+            lists = mine;
+            kk = m->k;
+        }
+        if ((rc = run_edge(m, l, X, xgs, lists, kk, P, cat + (int64_t)kCatOff[l] * NODES, cgs, b, st)) != PCD_OK) return rc;
+    }
+    {   // conv7 + bn7 + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
+        GemmArgs a = conv_args(m->wt[6], m->emb, 1024, cat, cgs, nullptr, 0, b);
+        a.epi = EPI_POOL; a.s = m->s[6]; a.t = m->t[6]; a.poolT = pooled;
+        a.pool_dbg = debug ? debug->pooled : nullptr;
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+    }
+    const float* hin = pooled;
+    float* hout[3] = {h1, h2, h3};
+    int K = 2 * m->emb;
+    for (int l = 0; l < 3; ++l) {
+        GemmArgs a = head_args(m->wt[7 + l], kHead[l], K, hin, hout[l], b);
+        a.epi = EPI_AFFINE_LRELU; a.s = m->s[7 + l]; a.t = m->t[7 + l];
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+        hin = hout[l];
+        K = kHead[l];
+    }
+    {   // linear4 (+ bias) -> out [b][out_ch]
+        GemmArgs a = head_args(m->wt[10], m->out_ch, 64, h3, out, b);
+        a.G = 1; a.ygs = m->out_ch; a.yms = 1;          // Y(m, n) = out[n * out_ch + m]
+        a.xgs = 1; a.xks = b;                           // X(k, n) = h3[k * b + n]
+        a.epi = EPI_AFFINE; a.s = m->s[10]; a.t = m->t[10];
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+    }
+    if (debug) {
+        if (debug->cat) PCD_HIP(hipMemcpyAsync(debug->cat, cat, b * cgs * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->lists)
+            PCD_HIP(hipMemcpyAsync(debug->lists, knn, 3 * b * NODES * m->k * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h1) PCD_HIP(hipMemcpyAsync(debug->h1, h1, 512 * b * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h2) PCD_HIP(hipMemcpyAsync(debug->h2, h2, 256 * b * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h3) PCD_HIP(hipMemcpyAsync(debug->h3, h3, 64 * b * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return PCD_OK;
+}
+
+int pcd_dgcnn_forward(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                      int64_t workspace_bytes, const pcd_dgcnn_debug* debug, void* stream) {
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, debug, nullptr, 0, stream);
+}
+
+int pcd_dgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                               int64_t workspace_bytes, const pcd_dgcnn_debug* debug, int32_t* first_bad,
+                               int64_t patch_base, void* stream) {
+    PCD_CHECK_ARG(first_bad != nullptr, "first_bad is null");
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, debug, first_bad, patch_base, stream);
+}
+
+int pcd_dgcnn_knn(const float* x, int64_t b, int channels, int k, int32_t* lists, void* stream) {
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(channels >= 1, "channels must be >= 1");
+    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(x != nullptr && lists != nullptr, "x / lists is null");
+    return run_knn(x, (int64_t)channels * NODES, channels, k, lists, b, as_stream(stream));
+}
+
+int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b, const int32_t* lists, int list_len,
+                       float* out, void* stream) {
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    PCD_CHECK_ARG(layer >= 1 && layer <= 6, "layer must be in [1, 6]");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(list_len >= 1 && list_len <= NODES, "list_len must be in [1, 64]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(x != nullptr && lists != nullptr && out != nullptr, "x / lists / out is null");
+    const int l = layer - 1;
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    float* P;
+    PCD_HIP(tmp.alloc(&P, b * 2 * kCout[l] * NODES * sizeof(float)));
+    const int rc = run_edge(m, l, x, (int64_t)kCin[l] * NODES, lists, list_len, P, out, (int64_t)kCout[l] * NODES, b, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64_t b, int nodes, int epilogue,
+                   const float* s, const float* t, float* y, void* stream) {
+    PCD_CHECK_ARG(m_rows >= 1 && k_cols >= 1, "M and K must be >= 1");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(nodes == NODES || nodes == 1, "nodes must be 64 (x [b][K][64]) or 1 (x [K][b])");
+    PCD_CHECK_ARG(epilogue >= EPI_PLAIN && epilogue <= EPI_AFFINE, "epilogue must be in [0, 3]");
+    PCD_CHECK_ARG(epilogue != EPI_POOL || nodes == NODES, "the pooling epilogue needs nodes = 64");
+    PCD_CHECK_ARG(epilogue == EPI_PLAIN || (s != nullptr && t != nullptr), "s / t is null");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(w != nullptr && x != nullptr && y != nullptr, "w / x / y is null");
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    float *Wt, *poolT = nullptr;
+    const int64_t wn = (int64_t)m_rows * k_cols;
+    PCD_HIP(tmp.alloc(&Wt, wn * sizeof(float)));
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)cdiv(wn, 256)), dim3(256), 0, st, w, m_rows, k_cols, Wt);
+    PCD_LAUNCH_CHECK();
+    GemmArgs a = nodes == NODES
+                     ? conv_args(Wt, m_rows, k_cols, x, (int64_t)k_cols * NODES, y, (int64_t)m_rows * NODES, b)
+                     : head_args(Wt, m_rows, k_cols, x, y, b);
+    a.epi = epilogue; a.s = s; a.t = t;
+    if (epilogue == EPI_POOL) {                        // y [b][2 M]
+        PCD_HIP(tmp.alloc(&poolT, 2 * (int64_t)m_rows * b * sizeof(float)));
+        a.poolT = poolT; a.pool_dbg = y; a.Y = nullptr;
+    }
+    const int rc = launch_gemm(a, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+}  // extern "C"

@@ -49,6 +49,21 @@ class DenoiseParams(ctypes.Structure):
                 ("phase_kind", c_int * 3), ("phase_alpha", c_float * 3), ("jacobi", c_int), ("clamp_global", c_float)]
 
 
+class DgcnnWeights(ctypes.Structure):
+    """Mirror of ``pcd_dgcnn_weights`` (include/pcd.h)."""
+    _fields_ = [("conv_w", c_void_p * 7), ("conv_rows", ctypes.c_int32 * 7), ("conv_cols", ctypes.c_int32 * 7),
+                ("bn_weight", c_void_p * 10), ("bn_bias", c_void_p * 10), ("bn_mean", c_void_p * 10),
+                ("bn_var", c_void_p * 10), ("bn_eps", c_double * 10), ("bn_len", ctypes.c_int32 * 10),
+                ("lin_w", c_void_p * 4), ("lin_b", c_void_p * 4), ("lin_rows", ctypes.c_int32 * 4),
+                ("lin_cols", ctypes.c_int32 * 4)]
+
+
+class DgcnnDebug(ctypes.Structure):
+    """Mirror of ``pcd_dgcnn_debug`` (include/pcd.h)."""
+    _fields_ = [("cat", c_void_p), ("lists", c_void_p), ("pooled", c_void_p), ("h1", c_void_p), ("h2", c_void_p),
+                ("h3", c_void_p)]
+
+
 # name -> (restype, argtypes); the exact export list of include/pcd.h
 _SIGS = {
     "pcd_last_error": (ctypes.c_char_p, []),
@@ -151,6 +166,17 @@ _SIGS = {
     "pcd_denoiser_set_readset": (c_int, [c_void_p, c_int]),
     "pcd_denoiser_readset_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "pcd_slab_iterate": (c_int, [c_void_p, c_void_p, POINTER(DenoiseParams), c_int, c_void_p]),
+    "pcd_dgcnn_create": (c_int, [POINTER(DgcnnWeights), c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "pcd_dgcnn_destroy": (c_int, [c_void_p]),
+    "pcd_dgcnn_workspace_bytes": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "pcd_dgcnn_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, POINTER(DgcnnDebug),
+                                  c_void_p]),
+    "pcd_dgcnn_forward_deferred": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                           POINTER(DgcnnDebug), c_void_p, c_int64, c_void_p]),
+    "pcd_dgcnn_knn": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "pcd_dgcnn_edgeconv": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "pcd_dgcnn_gemm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "pcd_orient_normals_mst": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
     "pcd_orient_normals_mst_gpu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "pcd_host_eigh3": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1074,3 +1100,151 @@ def orient_normals_mst_gpu(pos, n, a, b) -> torch.Tensor:
     check(lib().pcd_orient_normals_mst_gpu(ptr(p), ptr(out), p.size(0), ptr(a), ptr(b), a.numel(),
                                            c_void_p(stream_ptr())), "pcd_orient_normals_mst_gpu")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- DGCNN forward
+DGCNN_CIN = (17, 64, 64, 128, 256, 256)
+DGCNN_COUT = (64, 64, 128, 256, 256, 256)
+EPI_PLAIN, EPI_AFFINE_LRELU, EPI_POOL, EPI_AFFINE = range(4)
+DGCNN_NO_BAD_PATCH = 0x7f7f7f7f      # PCD_DGCNN_NO_BAD_PATCH
+
+
+class Dgcnn:
+    """Packed device weights of one DGCNN (pcd_dgcnn) and its forward.
+
+    conv: 7 weights [out, 2 in] (conv7 [emb, 1024]); bn: 10 tuples (weight, bias, running_mean, running_var, eps);
+    lin: 4 tuples (weight [out, in], bias or None).  The tensors may live on the host or the device (float32); they
+    are copied."""
+
+    def __init__(self, conv, bn, lin, k, init_dims, emb_dims, output_channels=3):
+        if len(conv) != 7 or len(bn) != 10 or len(lin) != 4:
+            raise ValueError("pcd: Dgcnn takes 7 convolution weights, 10 batch norms and 4 linears")
+        keep = []
+
+        def p32(t):
+            t = t.detach()
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        w = DgcnnWeights()
+        for i, cw in enumerate(conv):
+            cw2 = cw.reshape(cw.shape[0], -1)
+            w.conv_w[i], w.conv_rows[i], w.conv_cols[i] = p32(cw2), cw2.shape[0], cw2.shape[1]
+        for i, (g, be, mu, var, eps) in enumerate(bn):
+            if not (g.numel() == be.numel() == mu.numel() == var.numel()):
+                raise ValueError(f"pcd: bn{i + 1}: weight, bias, running_mean and running_var differ in length")
+            w.bn_weight[i], w.bn_bias[i], w.bn_mean[i], w.bn_var[i] = p32(g), p32(be), p32(mu), p32(var)
+            w.bn_eps[i], w.bn_len[i] = float(eps), g.numel()
+        for i, (lw, lb) in enumerate(lin):
+            if lw.dim() != 2 or (lb is not None and lb.numel() != lw.shape[0]):
+                raise ValueError(f"pcd: linear{i + 1}: weight must be [out, in] and the bias [out]")
+            w.lin_w[i], w.lin_rows[i], w.lin_cols[i] = p32(lw), lw.shape[0], lw.shape[1]
+            w.lin_b[i] = None if lb is None else p32(lb)
+        h = c_void_p()
+        device()
+        check(lib().pcd_dgcnn_create(ctypes.byref(w), int(k), int(init_dims), int(emb_dims), int(output_channels),
+                                     ctypes.byref(h)), "pcd_dgcnn_create")
+        self.handle = h
+        self.k, self.emb_dims, self.output_channels = int(k), int(emb_dims), int(output_channels)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.pcd_dgcnn_destroy(h)
+            self.handle = None
+
+    def workspace_bytes(self, b: int) -> int:
+        v = c_int64(0)
+        check(lib().pcd_dgcnn_workspace_bytes(self.handle, int(b), ctypes.byref(v)), "pcd_dgcnn_workspace_bytes")
+        return v.value
+
+    def workspace(self, b: int) -> torch.Tensor:
+        return torch.empty(max(self.workspace_bytes(b), 1), dtype=torch.uint8, device=device())
+
+    def forward(self, inputs: torch.Tensor, workspace: torch.Tensor = None, debug: bool = False,
+                first_bad: torch.Tensor = None, patch_base: int = 0):
+        """inputs [b, 20, 64] float32 on the device -> out [b, output_channels]; with debug also a dict of the
+        intermediate tensors (pcd_dgcnn_debug).  workspace: a contiguous device tensor of workspace_bytes(b) bytes or
+        more, on the inputs' device.  first_bad: None -- a bad index column raises ValueError (one stream synchronise
+        per call); or an int32 [1] device tensor holding DGCNN_NO_BAD_PATCH -- nothing waits for the device, and the
+        tensor takes the lowest patch_base + patch with a bad index column (pcd_dgcnn_forward_deferred)."""
+        x = f32(inputs)
+        if x.dim() != 3 or x.size(1) != 20 or x.size(2) != 64:
+            raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
+        b, dev = x.size(0), x.device
+        ws = self.workspace(b) if workspace is None else workspace
+        if not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous():
+            raise ValueError(f"pcd: DGCNN workspace must be a contiguous tensor on {dev}, got "
+                             f"{getattr(ws, 'device', type(ws).__name__)}")
+        if first_bad is not None and (not isinstance(first_bad, torch.Tensor) or first_bad.device != dev
+                                      or first_bad.dtype != torch.int32 or first_bad.numel() != 1):
+            raise ValueError(f"pcd: DGCNN first_bad must be an int32 tensor of one element on {dev}")
+        out = torch.empty((b, self.output_channels), dtype=torch.float32, device=dev)
+        dbg, d = None, None
+        if debug:
+            d = {"cat": torch.empty((b, 1024, 64), dtype=torch.float32, device=dev),
+                 "lists": torch.empty((3, b, 64, self.k), dtype=torch.int32, device=dev),
+                 "pooled": torch.empty((b, 2 * self.emb_dims), dtype=torch.float32, device=dev),
+                 "h1": torch.empty((512, b), dtype=torch.float32, device=dev),
+                 "h2": torch.empty((256, b), dtype=torch.float32, device=dev),
+                 "h3": torch.empty((64, b), dtype=torch.float32, device=dev)}
+            dbg = DgcnnDebug(*[d[n].data_ptr() for n in ("cat", "lists", "pooled", "h1", "h2", "h3")])
+        dbg_ref = None if dbg is None else ctypes.byref(dbg)
+        if first_bad is None:
+            check(lib().pcd_dgcnn_forward(self.handle, ptr(x), b, ptr(out), ptr(ws), ws.numel() * ws.element_size(),
+                                          dbg_ref, c_void_p(stream_ptr())), "pcd_dgcnn_forward")
+        else:
+            check(lib().pcd_dgcnn_forward_deferred(self.handle, ptr(x), b, ptr(out), ptr(ws),
+                                                   ws.numel() * ws.element_size(), dbg_ref, ptr(first_bad),
+                                                   int(patch_base), c_void_p(stream_ptr())),
+                  "pcd_dgcnn_forward_deferred")
+        return (out, d) if debug else out
+
+    def edgeconv(self, layer: int, x: torch.Tensor, lists: torch.Tensor) -> torch.Tensor:
+        """Layer 1-6 on x [b, Cin, 64] with neighbour lists int32 [b, 64, n] -> [b, Cout, 64] (pcd_dgcnn_edgeconv)."""
+        if not 1 <= int(layer) <= 6:
+            raise ValueError("pcd: DGCNN edge layers are 1-6")
+        x, lists = f32(x), on_device(lists, torch.int32)
+        b = x.size(0)
+        if tuple(x.shape) != (b, DGCNN_CIN[layer - 1], 64) or lists.dim() != 3 or tuple(lists.shape[:2]) != (b, 64):
+            raise ValueError(f"pcd: edgeconv layer {layer}: x {tuple(x.shape)} / lists {tuple(lists.shape)} do not fit")
+        out = torch.empty((b, DGCNN_COUT[layer - 1], 64), dtype=torch.float32, device=x.device)
+        check(lib().pcd_dgcnn_edgeconv(self.handle, int(layer), ptr(x), b, ptr(lists), lists.size(2), ptr(out),
+                                       c_void_p(stream_ptr())), "pcd_dgcnn_edgeconv")
+        return out
+
+
+def dgcnn_knn(x: torch.Tensor, k: int) -> torch.Tensor:
+    """x [b, C, 64] -> int32 [b, 64, k]: each row's k nearest rows in feature space (pcd_dgcnn_knn)."""
+    x = f32(x)
+    if x.dim() != 3 or x.size(2) != 64:
+        raise ValueError(f"pcd: dgcnn_knn takes [b, C, 64], got {tuple(x.shape)}")
+    lists = torch.empty((x.size(0), 64, int(k)), dtype=torch.int32, device=x.device)
+    check(lib().pcd_dgcnn_knn(ptr(x), x.size(0), x.size(1), int(k), ptr(lists), c_void_p(stream_ptr())),
+          "pcd_dgcnn_knn")
+    return lists
+
+
+def dgcnn_gemm(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=None, t=None) -> torch.Tensor:
+    """w [M, K] . x on the network's MFMA GEMM (pcd_dgcnn_gemm): x [b, K, 64] -> [b, M, 64] ([b, 2 M] with the
+    pooling epilogue), or x [K, b] -> [M, b]."""
+    w, x = f32(w), f32(x)
+    M, K = w.shape
+    if x.dim() == 3:
+        b, nodes = x.size(0), 64
+        if tuple(x.shape) != (b, K, 64):
+            raise ValueError(f"pcd: dgcnn_gemm: x {tuple(x.shape)} does not fit w {tuple(w.shape)}")
+        shape = (b, 2 * M) if epilogue == EPI_POOL else (b, M, 64)
+    else:
+        b, nodes = x.size(1), 1
+        if x.dim() != 2 or x.size(0) != K:
+            raise ValueError(f"pcd: dgcnn_gemm: x {tuple(x.shape)} does not fit w {tuple(w.shape)}")
+        shape = (M, b)
+    s = None if s is None else f32(s)
+    t = None if t is None else f32(t)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    check(lib().pcd_dgcnn_gemm(ptr(w), ptr(x), M, K, b, nodes, int(epilogue), ptr(s), ptr(t), ptr(y),
+                               c_void_p(stream_ptr())), "pcd_dgcnn_gemm")
+    return y
