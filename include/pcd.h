@@ -30,6 +30,9 @@
  *                                   MeshNormalFiltering::updateFilteredNormalsWithPredictedNormal and its helpers
  *                                                       src/GCNDenoiser/GCNDenoiser/MeshNormalFiltering.cpp:47-244
  *   pcd_dgcnn_*                     DGCNN.forward (eval)                       PatchGeneration/Modules/Network/GCNModel.py:121-215
+ *   pcd_dgcnn_train_* / _wgrad / _edgeconv_train(_backward)
+ *                                   DGCNN.forward (train) and loss.backward()  PatchGeneration/Modules/Network/GCNModel.py:170-207
+ *                                                                              PatchGeneration/Modules/NetworkController.py:120-136
  *   pcd_denoiser_*                  Processor.denoise / getMyFeatureDecomposition / denoiseUntilMinimumError loop body
  *                                                                              Pointcloud/Modules/Processor.py:110-185
  *   pcd_orient_normals_mst          GraphBuilder.flipNormals (MST + DFS, host) Pointcloud/Modules/GraphBuilder.py:129-209
@@ -561,6 +564,69 @@ int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b,
  * over each patch's 64 columns -> y [b][2 M]; 3: s[m] y + t[m].  Synchronises `stream`. */
 int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64_t b, int nodes, int epilogue,
                    const float* s, const float* t, float* y, void* stream);
+/* epilogue 4 of pcd_dgcnn_gemm: y += w . x, added into what y holds (the data gradients of the training step) */
+
+/* ------------------------------------------------------------------ DGCNN training (train(), fp32) */
+/* conv1-7 and the max / mean pooling of DGCNN.forward with self.training (GCNModel.py:170-207): batch norms take the
+ * batch's statistics (biased variance over every edge of the batch; sums in double, fixed order) and update their
+ * running buffers as nn.BatchNorm does (momentum, unbiased variance, num_batches_tracked).  The head (linear1-4,
+ * bn8-10, dropout) is not here.  Neighbour lists are constants of the backward; there is no gradient with respect
+ * to the inputs.  The same batch, weights and buffers give the same bits in every run; the bits depend on the batch. */
+typedef struct {
+    /* DEVICE pointers.  conv 1-7 weights as pcd_dgcnn_weights; batch norms 1-7.  bn_mean / bn_var / bn_tracked are
+     * updated in place (null: not updated; mean and var go together). */
+    const float* conv_w[7];
+    const float* bn_weight[7];
+    const float* bn_bias[7];
+    float* bn_mean[7];
+    float* bn_var[7];
+    int64_t* bn_tracked[7];
+    double bn_eps[7];
+    double bn_momentum[7];
+} pcd_dgcnn_train_params;
+typedef struct {
+    /* DEVICE outputs, overwritten: conv [out][2 in] (conv7 [emb][1024]), batch norm weight and bias gradients */
+    float* conv_w[7];
+    float* bn_weight[7];
+    float* bn_bias[7];
+} pcd_dgcnn_train_grads;
+/* bytes of caller-owned device scratch a training step of b patches needs: the packed weights plus about
+ * (1.2 MB + 260 B x emb) a patch; it carries the forward's state to the backward */
+int pcd_dgcnn_train_workspace_bytes(int k, int emb_dims, int64_t b, int64_t* bytes);
+/* inputs [b][20][64] -> pooled [b][2 emb] (max, then mean over the nodes, of conv7's activations).  Packs the split
+ * weights from prm on the stream (nothing goes to the host), keeps what the backward needs in the workspace and, if
+ * lists is not null, copies the neighbour lists of layers 4-6 to it ([3][b][64][k]).  A bad index column is
+ * PCD_ERR_ARG as in pcd_dgcnn_forward, before any buffer is updated; a short or misaligned workspace is PCD_ERR_ARG
+ * with nothing written.  Synchronises `stream` once, after the index check.
+ * Replaces dgcnn.train(); dgcnn(inputs) up to GCNModel.py:207 (NetworkController.py:120-122). */
+int pcd_dgcnn_train_forward(const pcd_dgcnn_train_params* prm, int k, int emb_dims, const float* inputs, int64_t b,
+                            float* pooled, void* workspace, int64_t workspace_bytes, int32_t* lists, void* stream);
+/* d_pooled [b][2 emb] -> the gradients of conv1-7's weights and bn1-7's weight and bias, from the workspace the
+ * forward of the same (k, emb_dims, inputs, b) left.  conv7_w: the weight the forward ran with.  Consumes the
+ * workspace (conv7's stored product becomes its gradient in place): one backward per forward.  Stream-ordered, never
+ * waits.  Replaces loss.backward() below the pooling (NetworkController.py:135). */
+int pcd_dgcnn_train_backward(int k, int emb_dims, const float* inputs, int64_t b, const float* d_pooled,
+                             const float* conv7_w, void* workspace, int64_t workspace_bytes,
+                             const pcd_dgcnn_train_grads* grads, void* stream);
+/* Stages, for tests.  wgrad: dw [M][K] = sum over the b x 64 columns of dy [b][M][64] x [b][K][64]^T on the exact-f32
+ * MFMA; the patches are split into runs of pcd_dgcnn_wgrad_split(b) whose partial products are added in run order
+ * (the conv weight gradients of loss.backward()).  Synchronises `stream`. */
+int pcd_dgcnn_wgrad(const float* dy, const float* x, int m_rows, int k_cols, int64_t b, float* dw, void* stream);
+int pcd_dgcnn_wgrad_split(int64_t b, int64_t* patches_per_split);
+/* One edge layer (1-6) in train() on x [b][Cin][64] with the given lists [b][64][list_len] (entries taken mod 64):
+ * w [Cout][2 Cin], gamma / beta [Cout] -> out [b][Cout][64], argmax [b][Cout][64] (the first maximal list slot),
+ * stats [3][Cout] doubles (mean, biased variance, 1 / sqrt(var + eps)); running_mean / running_var / tracked (null:
+ * none) are updated.  convN + max of GCNModel.py:178-200.  Synchronises `stream`. */
+int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* beta, double eps, double momentum,
+                             float* running_mean, float* running_var, int64_t* tracked, int layer, const float* x,
+                             int64_t b, const int32_t* lists, int list_len, float* out, uint8_t* argmax, double* stats,
+                             void* stream);
+/* Its backward (the forward is run again inside; no buffer is touched): g [b][Cout][64] = dL/d out -> dab
+ * [b][2 Cout][64] (dA rows, then dB rows), dgamma / dbeta [Cout], dw [Cout][2 Cin], and, if dx is not null,
+ * dx [b][Cin][64] with the lists held constant.  Synchronises `stream`. */
+int pcd_dgcnn_edgeconv_train_backward(const float* w, const float* gamma, const float* beta, double eps, int layer,
+                                      const float* x, int64_t b, const int32_t* lists, int list_len, const float* g,
+                                      float* dab, float* dgamma, float* dbeta, float* dw, float* dx, void* stream);
 
 /* ------------------------------------------------------------------ normal orientation (host) */
 /* GraphBuilder.flipNormals: Kruskal MST on cost 1-|n_i·n_j| over the directed edge list (a[e] -> b[e],

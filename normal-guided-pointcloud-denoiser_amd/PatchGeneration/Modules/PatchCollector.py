@@ -10,8 +10,8 @@ chunks as device tensors, so a large mesh never holds all of its 10 KB-per-face 
 `predictNormals(model)` takes those chunks through the network (Network/GCNModel.py, csrc/dgcnn.hip) and back to the
 mesh's frame, ready for Mesh.denoise(guided_normals=...).
 
-The file-system half of the reference class (savePatches, .mat files, directory scanning) and the training are not
-part of this package.  INTEGRATION.md lists where the output differs from the reference's on purpose
+The file-system half of the reference class (savePatches, .mat files, directory scanning) is not part of this
+package; PatchDataset.trainingBatches hands NetworkController.NetworkTrainer its batches.  INTEGRATION.md lists where the output differs from the reference's on purpose
 (boundary faces, non-manifold edges, degenerate faces, the sign of the middle axis).
 """
 from __future__ import annotations
@@ -110,6 +110,26 @@ class PatchDataset(torch.utils.data.Dataset):
         if o.shape != (self.SIZE, 3):
             raise ValueError(f"PatchDataset: outputs must have shape ({self.SIZE}, 3), got {o.shape}")
         return np.einsum("nij,ni->nj", self.data_rotations, o)
+
+    def trainingBatches(self, gt_normals, device=None, aligned=False, batch_size=None):
+        """The batches NetworkController.NetworkTrainer takes: a list of (inputs [b, 64, 20] float32, gt [b, 3]
+        float32) device tensors, batch_size patches each (default self.batch_size; a short last batch is dropped, as
+        the reference's loaders drop it).  gt_normals [n, 3] are the ground-truth normals of the patches' faces in
+        the mesh's frame -- each is taken into its patch's aligned frame with R n, the inverse of unalign -- or, with
+        aligned=True, already in the aligned frame.  Rows and normals are uploaded once; every batch is a view of
+        that one device copy, so an epoch over the list moves nothing between host and device."""
+        dev = _nat.device() if device is None else torch.device(device)
+        gt = np.asarray(gt_normals, dtype=np.float64)
+        if gt.shape != (self.SIZE, 3):
+            raise ValueError(f"PatchDataset: gt_normals must have shape ({self.SIZE}, 3), got {gt.shape}")
+        if not aligned:
+            gt = np.einsum("nij,nj->ni", self.data_rotations, gt)
+        bs = int(self.batch_size if batch_size is None else batch_size)
+        if bs < 1:
+            raise ValueError(f"PatchDataset: batch_size must be at least 1, got {bs}")
+        x = torch.as_tensor(self.data_patch).to(dev, torch.float32)
+        g = torch.as_tensor(gt).to(dev, torch.float32)
+        return [(x[s:s + bs], g[s:s + bs]) for s in range(0, self.SIZE - bs + 1, bs)]
 
 
 class PatchCollector:

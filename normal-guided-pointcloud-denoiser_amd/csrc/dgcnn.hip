@@ -3,7 +3,9 @@
 //   gemm_kernel    Y = W . X on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per output), 128 x 64
 //                  tiles, W shared by all patches, X the patches' columns.  Epilogues: plain store, per-row affine
 //                  (+ LeakyReLU 0.2), or affine + LeakyReLU + max / mean over the 64 columns of a patch (conv7:
-//                  [b, emb, 64] is never stored).
+//                  [b, emb, 64] is never stored); or added into Y (the data gradients of csrc/dgcnn_train.hip).
+//                  gemm_kernel<0> is the inference kernel; gemm_kernel<8> (train-mode forward products) joins float32
+//                  chains of 8 k in double.
 //   index_kernel   the three index columns (floats) -> int32 lists, truncating as .long() does; a value outside
 //                  [0, 63] or a NaN is clamped to 0 and the lowest such patch raised in a device flag.
 //   knn_kernel     one workgroup per patch: 64 x 64 squared distances of the layer's input, the k smallest per row,
@@ -19,6 +21,7 @@
 
 #include <vector>
 
+#include "pcd_dgcnn.h"
 #include "pcd_host.h"
 
 using namespace pcd;
@@ -29,7 +32,11 @@ constexpr int NODES = 64;            // rows of a patch
 constexpr int BM = 128, BN = 64, BK = 32;
 // LDS row strides (floats) of the W and X tiles: = 32 mod 64, so the two k rows an MFMA reads fall in different bank halves
 constexpr int LDA = 160, LDB = 96;
-constexpr int EPI_PLAIN = 0, EPI_AFFINE_LRELU = 1, EPI_POOL = 2, EPI_AFFINE = 3;
+using dgcnn::EPI_PLAIN;
+using dgcnn::EPI_AFFINE_LRELU;
+using dgcnn::EPI_POOL;
+using dgcnn::EPI_AFFINE;
+using dgcnn::EPI_ADD;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -49,6 +56,10 @@ __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v;
 // max that keeps a NaN (torch's max does)
 __device__ __forceinline__ float nanmax(float a, float b) { return (b > a || b != b) ? b : a; }
 
+// FLUSH = 0: the forward's kernel, one float32 chain over all of K.  FLUSH > 0 (the train-mode forward products, whose
+// rounding the batch norms of a small batch amplify): every FLUSH k the MFMA accumulators are added into double
+// accumulators and cleared, so no float32 chain is longer than FLUSH terms; plain epilogue only.
+template <int FLUSH>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
     // K-tiles of W [BK][BM] and X [BK][BN]; afterwards the pooling epilogue's [BM][65] staging
     __shared__ float lds[BM * 65];
@@ -82,6 +93,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
     f32x16 acc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+    double wide[FLUSH > 0 ? 2 : 1][FLUSH > 0 ? 16 : 1];
+    if constexpr (FLUSH > 0) {
+        static_assert(FLUSH % 2 == 0 && BK % FLUSH == 0, "a K tile is a whole number of flushes");
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wide[0][r] = wide[1][r] = 0.0;
+    }
     fetch(0);
     const int arow = lane >> 5, acol = lane & 31;
     for (int k0 = 0; k0 < a.K; k0 += BK) {
@@ -98,8 +115,25 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             const float bv = Bs[(kk + arow) * LDB + wn + acol];
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc[1], 0, 0, 0);
+            if constexpr (FLUSH > 0) {
+                if ((kk + 2) % FLUSH == 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        wide[0][r] += (double)acc[0][r];
+                        wide[1][r] += (double)acc[1][r];
+                        acc[0][r] = acc[1][r] = 0.f;
+                    }
+                }
+            }
         }
         __syncthreads();
+    }
+    if constexpr (FLUSH > 0) {                         // (every tile ends on a flush: the float accumulators are zero)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[0][r] = (float)wide[0][r];
+            acc[1][r] = (float)wide[1][r];
+        }
     }
     // C layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int cn = wn + acol;
@@ -112,14 +146,15 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             const int rm = wm + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * arow;
             const int m = m0 + rm;
             float v = acc[h][r];
-            if (a.epi != EPI_PLAIN && m < a.M) {
+            if (a.epi != EPI_PLAIN && a.epi != EPI_ADD && m < a.M) {
                 v = fmaf(a.s[m], v, a.t[m]);
                 if (a.epi != EPI_AFFINE) v = lrelu(v);
             }
             if (a.epi == EPI_POOL) {
                 Ps[rm * 65 + cn] = v;
             } else if (m < a.M && n < a.N) {
-                a.Y[(n / a.G) * a.ygs + (int64_t)m * a.yms + n % a.G] = v;
+                float* y = a.Y + (n / a.G) * a.ygs + (int64_t)m * a.yms + n % a.G;
+                *y = a.epi == EPI_ADD ? *y + v : v;
             }
         }
     }
@@ -243,10 +278,15 @@ const int kCout[6] = {64, 64, 128, 256, 256, 256};
 const int kCatOff[6] = {0, 64, 128, 256, 512, 768};   // the layer's slice of the [1024][64] concatenation
 const int kHead[3] = {512, 256, 64};
 
-int launch_gemm(const GemmArgs& a, hipStream_t st) {
+constexpr int kWideFlush = 8;        // k per float32 chain of the train-mode forward products
+
+int launch_gemm(const GemmArgs& a, hipStream_t st, bool wide = false) {
     if (a.N <= 0 || a.M <= 0) return PCD_OK;
     dim3 grid((unsigned)cdiv(a.N, BN), (unsigned)cdiv(a.M, BM));
-    hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, st, a);
+    if (wide)
+        hipLaunchKernelGGL(gemm_kernel<kWideFlush>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(gemm_kernel<0>, grid, dim3(256), 0, st, a);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
@@ -321,6 +361,36 @@ constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
 constexpr int64_t kMaxBatch = 1 << 20;   // 2^31 / (64 x 20) patches and more would pass int32 in the index flag
 
 }  // namespace
+
+// what csrc/dgcnn_train.hip shares with the forward (pcd_dgcnn.h)
+namespace pcd {
+namespace dgcnn {
+
+int conv_gemm(const float* Wt, int M, int K, const float* X, int64_t xgs, float* Y, int64_t ygs, int64_t b, int epi,
+              bool wide, hipStream_t st) {
+    GemmArgs a = conv_args(Wt, M, K, X, xgs, Y, ygs, b);
+    a.epi = epi;
+    return launch_gemm(a, st, wide && epi == EPI_PLAIN);
+}
+
+int knn(const float* x, int64_t xgs, int C, int k, int32_t* lists, int64_t b, hipStream_t st) {
+    return run_knn(x, xgs, C, k, lists, b, st);
+}
+
+int index_lists(const float* inputs, int64_t b, int32_t* lists, int* flag, hipStream_t st) {
+    hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, lists, flag, 0);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+int transpose(const float* W, int M, int K, float* Wt, hipStream_t st) {
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, W, M, K, Wt);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+}  // namespace dgcnn
+}  // namespace pcd
 
 extern "C" {
 
@@ -595,9 +665,9 @@ int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64
     PCD_CHECK_ARG(m_rows >= 1 && k_cols >= 1, "M and K must be >= 1");
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
     PCD_CHECK_ARG(nodes == NODES || nodes == 1, "nodes must be 64 (x [b][K][64]) or 1 (x [K][b])");
-    PCD_CHECK_ARG(epilogue >= EPI_PLAIN && epilogue <= EPI_AFFINE, "epilogue must be in [0, 3]");
+    PCD_CHECK_ARG(epilogue >= EPI_PLAIN && epilogue <= EPI_ADD, "epilogue must be in [0, 4]");
     PCD_CHECK_ARG(epilogue != EPI_POOL || nodes == NODES, "the pooling epilogue needs nodes = 64");
-    PCD_CHECK_ARG(epilogue == EPI_PLAIN || (s != nullptr && t != nullptr), "s / t is null");
+    PCD_CHECK_ARG(epilogue == EPI_PLAIN || epilogue == EPI_ADD || (s != nullptr && t != nullptr), "s / t is null");
     if (b == 0) return PCD_OK;
     PCD_CHECK_ARG(w != nullptr && x != nullptr && y != nullptr, "w / x / y is null");
     hipStream_t st = as_stream(stream);

@@ -1,0 +1,882 @@
+// DGCNN in train(): conv1-7 with batch-statistic batch norms and the max / mean pooling, forward and backward
+// (GCNModel.py:170-207 with self.training, and what loss.backward() of NetworkController.py:135 does to it).
+//
+//   pack_edge_kernel        conv weight [Cout][2 Cin] -> [W_a ; W_b - W_a] as [Cin][2 Cout] (forward) and [2 Cout][Cin]
+//                           (data gradient), on the stream: an optimiser step never sends a weight to the host.
+//   edge_stats_kernel       per channel sum and sum of squares of y = A[nbr] + B over a chunk of patches, in double
+//   row_stats_kernel        the same over the rows of conv7's product
+//   bn_finalize_kernel      chunk partials, in chunk order -> (mu, var, 1 / sigma), (s, t), running buffers
+//   edge_train_kernel       edge_kernel of the forward plus the arg-max slot (first maximal, one byte); the edge value,
+//                           the affine and the max in double, rounded once
+//   pool_train_kernel       conv7: affine (double), LeakyReLU, max (first arg-max node) and mean over the 64 nodes
+//   *_bwd_reduce_kernel     d beta, d gamma partials per chunk, in double
+//   bn_bwd_finalize_kernel  partials in chunk order -> d beta, d gamma
+//   reverse_lists_kernel    the edges of a patch grouped by their target node, (i, j) order kept
+//   edge_bwd_apply_kernel   dy on every edge -> dB (a row's own list) and dA (the target's incoming edges, in order)
+//   pool_bwd_apply_kernel   conv7: dY in place of Y
+//   wgrad_kernel            dW [M][K] = sum_n dY[M][n] X[K][n] on the exact-f32 MFMA, the reduction over patches split
+//                           across workgroups into partial tiles; wgrad_reduce_kernel adds them in split order
+//
+// No float atomics; every sum has a fixed order that depends on b alone.  The forward products run on gemm_kernel<8>
+// (dgcnn.hip: float32 chains of 8 k joined in double, rounded once -- the batch norms of a small batch multiply the
+// forward's rounding by up to 1 / sqrt(eps)); the data gradients W^T dY on the forward's own gemm_kernel<0> with the
+// add-into-Y epilogue.  -ffp-contract=off stays: fmaf where a fused multiply-add is meant.
+#include <math.h>
+
+#include <algorithm>
+
+#include "pcd_dgcnn.h"
+#include "pcd_host.h"
+
+using namespace pcd;
+
+namespace {
+
+constexpr int NODES = 64;
+constexpr int CHUNK = 8;             // patches per partial of the batch statistics
+const int kCin[6] = {17, 64, 64, 128, 256, 256};
+const int kCout[6] = {64, 64, 128, 256, 256, 256};
+const int kCatOff[6] = {0, 64, 128, 256, 512, 768};
+constexpr int64_t kMaxBatch = 1 << 20;
+constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
+// An edge value y = A[j] + B[i] and its normalised z = s y + t are formed in double from the stored float32 products
+// and the double statistics (s = gamma / sigma, t = beta - s mu), and rounded once where they are stored: the forward,
+// the statistics and the backward all see the same y and the same sign of z.
+__device__ __forceinline__ double edge_y(float a, float b) { return (double)a + (double)b; }
+__device__ __forceinline__ double affine(double y, double s, double t) { return fma(s, y, t); }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);   // a fixed tree; every lane ends with the same bits
+    return v;
+}
+
+// W [Cout][2 Cin] -> Wt [Cin][2 Cout] and Ws [2 Cout][Cin] of [W_a ; W_b - W_a]
+__global__ void pack_edge_kernel(const float* W, int Cin, int Cout, float* Wt, float* Ws) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= Cin * Cout) return;
+    const int c = e / Cin, k = e % Cin;
+    const float wa = W[(int64_t)c * 2 * Cin + k];
+    const float wd = W[(int64_t)c * 2 * Cin + Cin + k] - wa;
+    Wt[(int64_t)k * 2 * Cout + c] = wa;
+    Wt[(int64_t)k * 2 * Cout + Cout + c] = wd;
+    Ws[(int64_t)c * Cin + k] = wa;
+    Ws[(int64_t)(Cout + c) * Cin + k] = wd;
+}
+
+// part [chunk][C][2]: sum and sum of squares of y over the chunk's edges (lane = row i, a wave per channel)
+__global__ __launch_bounds__(256) void edge_stats_kernel(const float* P, int Cout, const int32_t* lists, int kk, int64_t b,
+                                                         double* part) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= Cout) return;
+    const int64_t p0 = (int64_t)blockIdx.x * CHUNK, p1 = min(b, p0 + CHUNK);
+    double s = 0.0, q = 0.0;
+    for (int64_t p = p0; p < p1; ++p) {
+        const float* A = P + (p * 2 * Cout + c) * NODES;
+        const float Bi = A[(int64_t)Cout * NODES + i];
+        const int32_t* row = lists + (p * NODES + i) * kk;
+        for (int j = 0; j < kk; ++j) {
+            const double y = edge_y(A[row[j] & 63], Bi);
+            s += y;
+            q = fma(y, y, q);
+        }
+    }
+    s = wave_sum(s);
+    q = wave_sum(q);
+    if (i == 0) {
+        part[((int64_t)blockIdx.x * Cout + c) * 2] = s;
+        part[((int64_t)blockIdx.x * Cout + c) * 2 + 1] = q;
+    }
+}
+
+// the same over Y [b][C][64]
+__global__ __launch_bounds__(256) void row_stats_kernel(const float* Y, int C, int64_t b, double* part) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;
+    const int64_t p0 = (int64_t)blockIdx.x * CHUNK, p1 = min(b, p0 + CHUNK);
+    double s = 0.0, q = 0.0;
+    for (int64_t p = p0; p < p1; ++p) {
+        const double y = (double)Y[(p * C + c) * NODES + i];
+        s += y;
+        q = fma(y, y, q);
+    }
+    s = wave_sum(s);
+    q = wave_sum(q);
+    if (i == 0) {
+        part[((int64_t)blockIdx.x * C + c) * 2] = s;
+        part[((int64_t)blockIdx.x * C + c) * 2 + 1] = q;
+    }
+}
+
+struct BnArgs {
+    const double* part;
+    int nchunks, C;
+    double N, eps, momentum;
+    const float *gamma, *beta;
+    float *rmean, *rvar;     // nullable: not updated
+    int64_t* tracked;        // nullable
+    double* stat;            // [3][C]: mu, biased var, 1 / sqrt(var + eps)
+    double* sti;             // [2][C]: s = gamma / sigma, t = beta - s mu
+};
+
+__global__ void bn_finalize_kernel(BnArgs a) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.C) return;
+    double s = 0.0, q = 0.0;
+    for (int ch = 0; ch < a.nchunks; ++ch) {
+        s += a.part[((int64_t)ch * a.C + c) * 2];
+        q += a.part[((int64_t)ch * a.C + c) * 2 + 1];
+    }
+    const double mu = s / a.N;
+    double var = q / a.N - mu * mu;
+    if (var < 0.0) var = 0.0;
+    const double istd = 1.0 / sqrt(var + a.eps);
+    const double sc = (double)a.gamma[c] * istd;
+    a.stat[c] = mu;
+    a.stat[a.C + c] = var;
+    a.stat[2 * a.C + c] = istd;
+    a.sti[c] = sc;
+    a.sti[a.C + c] = (double)a.beta[c] - sc * mu;
+    if (a.rmean) a.rmean[c] = (float)((1.0 - a.momentum) * (double)a.rmean[c] + a.momentum * mu);
+    if (a.rvar) a.rvar[c] = (float)((1.0 - a.momentum) * (double)a.rvar[c] + a.momentum * (var * (a.N / (a.N - 1.0))));
+    if (c == 0 && a.tracked) *a.tracked += 1;
+}
+
+// out[c][i] = lrelu(max_j (s_c (A[c][nbr(i, j)] + B[c][i]) + t_c)), the max taken in double; arg: the first maximal slot
+__global__ __launch_bounds__(256) void edge_train_kernel(const float* P, int Cout, const int32_t* lists, int kk,
+                                                         const double* sti, float* out, int64_t ogs, uint8_t* arg,
+                                                         int64_t ags) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= Cout) return;
+    const int64_t p = blockIdx.x;
+    const float* A = P + (p * 2 * Cout + c) * NODES;
+    const float Bi = A[(int64_t)Cout * NODES + i];
+    const double sc = sti[c], tc = sti[Cout + c];
+    const int32_t* row = lists + (p * NODES + i) * kk;
+    double m = -INFINITY;
+    int at = 0;
+    for (int j = 0; j < kk; ++j) {
+        const double v = affine(edge_y(A[row[j] & 63], Bi), sc, tc);
+        if (v > m || (v != v && m == m)) {               // a NaN wins once, as torch's max keeps it
+            m = v;
+            at = j;
+        }
+    }
+    out[p * ogs + (int64_t)c * NODES + i] = lrelu((float)m);
+    arg[p * ags + (int64_t)c * NODES + i] = (uint8_t)at;
+}
+
+// (value, node) ordered: the greater value, then the lower node; a NaN above every number
+__device__ __forceinline__ bool takes(float ov, int oi, float v, int i) {
+    const bool on = ov != ov, vn = v != v;
+    if (on != vn) return on;
+    if (on) return oi < i;
+    return ov > v || (ov == v && oi < i);
+}
+
+// Y [b][C][64] -> pooled [b][2 C] (max, then mean of lrelu(s y + t)), arg7 [b][C] the first arg-max node
+__global__ __launch_bounds__(256) void pool_train_kernel(const float* Y, int C, const double* sti, float* pooled,
+                                                         uint8_t* arg7) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;
+    const int64_t p = blockIdx.x;
+    const float v = lrelu((float)affine((double)Y[(p * C + c) * NODES + i], sti[c], sti[C + c]));
+    float m = v;
+    double sum = (double)v;
+    int at = i;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(m, off);
+        const int oi = __shfl_xor(at, off);
+        if (takes(ov, oi, m, at)) {
+            m = ov;
+            at = oi;
+        }
+        sum += __shfl_xor(sum, off);
+    }
+    if (i == 0) {
+        pooled[p * 2 * C + c] = m;
+        pooled[p * 2 * C + C + c] = (float)(sum * (1.0 / NODES));
+        arg7[p * C + c] = (uint8_t)at;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+// part [chunk][C][2]: sum of dz*, sum of dz* yhat* over the chunk's rows
+__global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* P, int Cout, const int32_t* lists, int kk,
+                                                              const uint8_t* arg, int64_t ags, const float* g, int64_t ggs,
+                                                              const double* stat, const double* sti, int64_t b,
+                                                              double* part) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= Cout) return;
+    const int64_t p0 = (int64_t)blockIdx.x * CHUNK, p1 = min(b, p0 + CHUNK);
+    const double sc = sti[c], tc = sti[Cout + c];
+    const double mu = stat[c], istd = stat[2 * Cout + c];
+    double sb = 0.0, sg = 0.0;
+    for (int64_t p = p0; p < p1; ++p) {
+        const float* A = P + (p * 2 * Cout + c) * NODES;
+        const float Bi = A[(int64_t)Cout * NODES + i];
+        const int js = min((int)arg[p * ags + (int64_t)c * NODES + i], kk - 1);
+        const double y = edge_y(A[lists[(p * NODES + i) * kk + js] & 63], Bi);
+        const float gz = g[p * ggs + (int64_t)c * NODES + i];
+        const float dz = (float)affine(y, sc, tc) > 0.f ? gz : 0.2f * gz;
+        sb += (double)dz;
+        sg = fma((double)dz, (y - mu) * istd, sg);
+    }
+    sb = wave_sum(sb);
+    sg = wave_sum(sg);
+    if (i == 0) {
+        part[((int64_t)blockIdx.x * Cout + c) * 2] = sb;
+        part[((int64_t)blockIdx.x * Cout + c) * 2 + 1] = sg;
+    }
+}
+
+// conv7: dz[p][c][i] = (gmax [i = arg7] + gmean / 64) lrelu'(s y + t); dpooled [b][2 C]
+__device__ __forceinline__ float pool_dz(float y, int i, int at, float gmax, float gmean, double sc, double tc) {
+    const float gz = (i == at ? gmax : 0.f) + gmean * (1.f / NODES);
+    return (float)affine((double)y, sc, tc) > 0.f ? gz : 0.2f * gz;
+}
+
+__global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float* Y, int C, const uint8_t* arg7,
+                                                              const float* dpooled, const double* stat, const double* sti,
+                                                              int64_t b, double* part) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;
+    const int64_t p0 = (int64_t)blockIdx.x * CHUNK, p1 = min(b, p0 + CHUNK);
+    const double sc = sti[c], tc = sti[C + c];
+    const double mu = stat[c], istd = stat[2 * C + c];
+    double sb = 0.0, sg = 0.0;
+    for (int64_t p = p0; p < p1; ++p) {
+        const float y = Y[(p * C + c) * NODES + i];
+        const float dz = pool_dz(y, i, arg7[p * C + c], dpooled[p * 2 * C + c], dpooled[p * 2 * C + C + c], sc, tc);
+        sb += (double)dz;
+        sg = fma((double)dz, ((double)y - mu) * istd, sg);
+    }
+    sb = wave_sum(sb);
+    sg = wave_sum(sg);
+    if (i == 0) {
+        part[((int64_t)blockIdx.x * C + c) * 2] = sb;
+        part[((int64_t)blockIdx.x * C + c) * 2 + 1] = sg;
+    }
+}
+
+// partials in chunk order -> dstat [2][C] (d beta, d gamma, double) and the float gradients
+__global__ void bn_bwd_finalize_kernel(const double* part, int nchunks, int C, double* dstat, float* dgamma, float* dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double sb = 0.0, sg = 0.0;
+    for (int ch = 0; ch < nchunks; ++ch) {
+        sb += part[((int64_t)ch * C + c) * 2];
+        sg += part[((int64_t)ch * C + c) * 2 + 1];
+    }
+    dstat[c] = sb;
+    dstat[C + c] = sg;
+    dbeta[c] = (float)sb;
+    dgamma[c] = (float)sg;
+}
+
+// Y [b][C][64] -> dY in place: s (dz - d beta / N - yhat d gamma / N)
+__global__ __launch_bounds__(256) void pool_bwd_apply_kernel(float* Y, int C, const uint8_t* arg7, const float* dpooled,
+                                                             const double* stat, const double* sti, const double* dstat,
+                                                             double invN) {
+    const int i = threadIdx.x & 63, c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;
+    const int64_t p = blockIdx.x;
+    const double sc = sti[c], tc = sti[C + c];
+    const double mu = stat[c], istd = stat[2 * C + c];
+    const double k1 = dstat[c] * invN, k2 = dstat[C + c] * invN;
+    float* at = Y + (p * C + c) * NODES + i;
+    const float y = *at;
+    const float dz = pool_dz(y, i, arg7[p * C + c], dpooled[p * 2 * C + c], dpooled[p * 2 * C + C + c], sc, tc);
+    *at = (float)(sc * (((double)dz - k1) - ((double)y - mu) * istd * k2));
+}
+
+// lists [b][64][kk] -> rev_off [b][65], rev [b][64 kk]: the edges (i << 8 | j) grouped by target, (i, j) order kept
+__global__ __launch_bounds__(64) void reverse_lists_kernel(const int32_t* lists, int kk, int32_t* rev_off, int32_t* rev) {
+    __shared__ uint8_t L[NODES * NODES];
+    __shared__ int cnt[NODES + 1];
+    const int64_t p = blockIdx.x;
+    const int v = threadIdx.x, E = NODES * kk;
+    for (int e = v; e < E; e += NODES) L[e] = (uint8_t)(lists[p * E + e] & 63);
+    __syncthreads();
+    int n = 0;
+    for (int e = 0; e < E; ++e) n += L[e] == v ? 1 : 0;
+    cnt[v + 1] = n;
+    __syncthreads();
+    if (v == 0) {
+        cnt[0] = 0;
+        for (int t = 1; t <= NODES; ++t) cnt[t] += cnt[t - 1];
+    }
+    __syncthreads();
+    int o = cnt[v];
+    rev_off[p * (NODES + 1) + v] = o;
+    if (v == NODES - 1) rev_off[p * (NODES + 1) + NODES] = cnt[NODES];
+    int e = 0;
+    for (int i = 0; i < NODES; ++i)
+        for (int j = 0; j < kk; ++j, ++e)
+            if (L[e] == v) rev[p * E + o++] = (i << 8) | j;
+}
+
+// dP [b][2 Cout][64]: dA rows, then dB rows
+__global__ __launch_bounds__(256) void edge_bwd_apply_kernel(const float* P, int Cout, const int32_t* lists, int kk,
+                                                             const int32_t* rev_off, const int32_t* rev,
+                                                             const uint8_t* arg, int64_t ags, const float* g, int64_t ggs,
+                                                             const double* stat, const double* sti, const double* dstat,
+                                                             double invN, float* dP) {
+    __shared__ float Bs[4][NODES];
+    __shared__ float dzs[4][NODES];
+    __shared__ uint8_t jss[4][NODES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int cr = blockIdx.y * 4 + w;
+    const bool live = cr < Cout;
+    const int c = live ? cr : 0;
+    const int64_t p = blockIdx.x;
+    const float* A = P + (p * 2 * Cout + c) * NODES;
+    const float Av = A[lane], Bi = A[(int64_t)Cout * NODES + lane];
+    const double sc = sti[c], tc = sti[Cout + c];
+    const double mu = stat[c], istd = stat[2 * Cout + c];
+    const double k1 = dstat[c] * invN, k2 = dstat[Cout + c] * invN;
+    const int32_t* row = lists + (p * NODES + lane) * kk;
+    const int js = min((int)arg[p * ags + (int64_t)c * NODES + lane], kk - 1);
+    const double ys = edge_y(A[row[js] & 63], Bi);
+    const float gz = g[p * ggs + (int64_t)c * NODES + lane];
+    const float dz = (float)affine(ys, sc, tc) > 0.f ? gz : 0.2f * gz;
+    Bs[w][lane] = Bi;
+    dzs[w][lane] = dz;
+    jss[w][lane] = (uint8_t)js;
+    __syncthreads();
+    // dB: lane = row i over its own list
+    double accB = 0.0;
+    for (int j = 0; j < kk; ++j) {
+        const double yh = (edge_y(A[row[j] & 63], Bi) - mu) * istd;
+        accB += ((j == js ? (double)dz : 0.0) - k1) - yh * k2;
+    }
+    // dA: lane = target v over its incoming edges
+    double accA = 0.0;
+    const int32_t* ro = rev_off + p * (NODES + 1);
+    const int32_t* rv = rev + p * NODES * kk;
+    const int e1 = ro[lane + 1];
+    for (int e = ro[lane]; e < e1; ++e) {
+        const int ij = rv[e], i = (ij >> 8) & 63, j = ij & 255;
+        const double yh = (edge_y(Av, Bs[w][i]) - mu) * istd;
+        accA += ((j == jss[w][i] ? (double)dzs[w][i] : 0.0) - k1) - yh * k2;
+    }
+    if (live) {
+        dP[(p * 2 * Cout + c) * NODES + lane] = (float)(sc * accA);
+        dP[(p * 2 * Cout + Cout + c) * NODES + lane] = (float)(sc * accB);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ weight gradient
+constexpr int WM = 128, WK = 64, WN = 32;
+// LDS row strides (floats), = 33 mod 64: the 32 n rows a wave writes land in 32 banks, and the two n rows an MFMA
+// reads fall in different bank halves but for one bank
+constexpr int WLA = 161, WLB = 97;
+
+struct WgradArgs {
+    const float* dY;         // dY(m, n) = dY[(n / 64) * ygs + m * 64 + n % 64]
+    const float* X;          // X(k, n)  = X[(n / 64) * xgs + k * 64 + n % 64]
+    float* part;             // [splits][M][K]
+    int64_t ygs, xgs, b, pps;
+    int M, K;
+};
+
+__global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
+    __shared__ float As[WN * WLA];   // [n][m]
+    __shared__ float Bs[WN * WLB];   // [n][k]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;
+    const int m0 = blockIdx.y * WM, k0 = blockIdx.z * WK;
+    const int64_t p0 = (int64_t)blockIdx.x * a.pps, p1 = min(a.b, p0 + a.pps);
+    const int nn = tid & 31, r0 = tid >> 5;              // this thread moves column nn of rows r0 + 8 r
+    const int arow = lane >> 5, acol = lane & 31;
+    f32x16 acc[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+    for (int64_t p = p0; p < p1; ++p) {
+        for (int h = 0; h < NODES; h += WN) {
+            float wr[16], xr[8];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + r0 + 8 * r;
+                wr[r] = m < a.M ? a.dY[p * a.ygs + (int64_t)m * NODES + h + nn] : 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int k = k0 + r0 + 8 * r;
+                xr[r] = k < a.K ? a.X[p * a.xgs + (int64_t)k * NODES + h + nn] : 0.f;
+            }
+            __syncthreads();                             // the previous step's MFMA reads are done
+#pragma unroll
+            for (int r = 0; r < 16; ++r) As[nn * WLA + r0 + 8 * r] = wr[r];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) Bs[nn * WLB + r0 + 8 * r] = xr[r];
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < WN; kk += 2) {
+                const float a0 = As[(kk + arow) * WLA + wm + acol];
+                const float a1 = As[(kk + arow) * WLA + wm + 32 + acol];
+                const float bv = Bs[(kk + arow) * WLB + wn + acol];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc[1], 0, 0, 0);
+            }
+        }
+    }
+    // C layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int k = k0 + wn + acol;
+    float* out = a.part + (int64_t)blockIdx.x * a.M * a.K;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * arow;
+            if (m < a.M && k < a.K) out[(int64_t)m * a.K + k] = acc[h][r];
+        }
+    }
+}
+
+// mode 0: out [M][K] = sum over splits, in split order.  mode 1 (M = 2 Cout, rows dW_A then dW_B of the split weight):
+// out [Cout][2 K] = [dW_A - dW_B | dW_B], the gradient of the module's [Cout][2 Cin] weight
+__global__ void wgrad_reduce_kernel(const float* part, int splits, int M, int K, float* out, int mode) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t MK = (int64_t)M * K;
+    if (mode == 0) {
+        if (e >= MK) return;
+        float s = 0.f;
+        for (int sp = 0; sp < splits; ++sp) s += part[sp * MK + e];
+        out[e] = s;
+    } else {
+        const int Cout = M / 2;
+        if (e >= (int64_t)Cout * K) return;
+        const int64_t c = e / K, k = e % K;
+        float sa = 0.f, sd = 0.f;
+        for (int sp = 0; sp < splits; ++sp) {
+            sa += part[sp * MK + e];
+            sd += part[sp * MK + (int64_t)Cout * K + e];
+        }
+        out[c * 2 * K + k] = sa - sd;
+        out[c * 2 * K + K + k] = sd;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+// patches per split of the weight gradient's reduction: at most 32 partial tiles, 4 patches or more each
+int64_t wgrad_pps(int64_t b) {
+    const int64_t s = std::max<int64_t>(1, std::min<int64_t>(32, cdiv(b, 4)));
+    return std::max<int64_t>(1, cdiv(b, s));
+}
+int64_t wgrad_splits(int64_t b) { return std::max<int64_t>(1, cdiv(b, wgrad_pps(b))); }
+
+int run_wgrad(const float* dY, int64_t ygs, int M, const float* X, int64_t xgs, int K, int64_t b, float* part, float* out,
+              int mode, hipStream_t st) {
+    WgradArgs a{};
+    a.dY = dY; a.X = X; a.part = part; a.ygs = ygs; a.xgs = xgs; a.b = b; a.pps = wgrad_pps(b); a.M = M; a.K = K;
+    const int splits = (int)wgrad_splits(b);
+    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)splits, (unsigned)cdiv(M, WM), (unsigned)cdiv(K, WK)), dim3(256), 0, st, a);
+    PCD_LAUNCH_CHECK();
+    const int64_t n = mode == 0 ? (int64_t)M * K : (int64_t)(M / 2) * K;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, part, splits, M, K, out, mode);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+struct Bn {                  // one batch norm's parameters and buffers (device)
+    const float *gamma, *beta;
+    float *rmean, *rvar;
+    int64_t* tracked;
+    double eps, momentum;
+};
+
+int run_finalize(const Bn& bn, const double* part, int64_t b, int C, double N, double* stat, double* sti, hipStream_t st) {
+    BnArgs a{};
+    a.part = part; a.nchunks = (int)cdiv(b, CHUNK); a.C = C; a.N = N; a.eps = bn.eps; a.momentum = bn.momentum;
+    a.gamma = bn.gamma; a.beta = bn.beta; a.rmean = bn.rmean; a.rvar = bn.rvar; a.tracked = bn.tracked;
+    a.stat = stat; a.sti = sti;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)cdiv(C, 64)), dim3(64), 0, st, a);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+// edge layer l forward: X -> P = [A ; B], statistics, out and the arg-max bytes
+int edge_forward(int l, const float* Wt, const Bn& bn, const float* X, int64_t xgs, const int32_t* lists, int kk, float* P,
+                 double* part, double* stat, double* sti, float* out, int64_t ogs, uint8_t* arg, int64_t ags, int64_t b,
+                 hipStream_t st) {
+    const int Cin = kCin[l], Cout = kCout[l];
+    int rc = dgcnn::conv_gemm(Wt, 2 * Cout, Cin, X, xgs, P, (int64_t)2 * Cout * NODES, b, dgcnn::EPI_PLAIN, true, st);
+    if (rc != PCD_OK) return rc;
+    const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(Cout, 4));
+    hipLaunchKernelGGL(edge_stats_kernel, chunks, dim3(256), 0, st, P, Cout, lists, kk, b, part);
+    PCD_LAUNCH_CHECK();
+    if ((rc = run_finalize(bn, part, b, Cout, (double)b * NODES * kk, stat, sti, st)) != PCD_OK) return rc;
+    hipLaunchKernelGGL(edge_train_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
+                       sti, out, ogs, arg, ags);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+// edge layer l backward: g = dL/d out -> d gamma, d beta, dP = [dA ; dB], dW (module layout), dX (null: not wanted)
+int edge_backward(int l, const float* Ws, const float* X, int64_t xgs, const int32_t* lists, int kk, const int32_t* rev_off,
+                  const int32_t* rev, const float* P, const uint8_t* arg, int64_t ags, const float* g, int64_t ggs,
+                  const double* stat, const double* sti, double* part, double* dstat, float* dP, float* wpart,
+                  float* dgamma, float* dbeta, float* dW, float* dX, int64_t dxgs, bool add, int64_t b, hipStream_t st) {
+    const int Cin = kCin[l], Cout = kCout[l];
+    const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(Cout, 4));
+    hipLaunchKernelGGL(edge_bwd_reduce_kernel, chunks, dim3(256), 0, st, P, Cout, lists, kk, arg, ags, g, ggs, stat, sti, b, part);
+    PCD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(Cout, 64)), dim3(64), 0, st, part, (int)cdiv(b, CHUNK), Cout,
+                       dstat, dgamma, dbeta);
+    PCD_LAUNCH_CHECK();
+    const double invN = 1.0 / ((double)b * NODES * kk);
+    hipLaunchKernelGGL(edge_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
+                       rev_off, rev, arg, ags, g, ggs, stat, sti, dstat, invN, dP);
+    PCD_LAUNCH_CHECK();
+    int rc;
+    if (dX) {   // dX (+)= [W_a ; W_b - W_a]^T dP: the split weight [2 Cout][Cin] is the GEMM's transposed operand
+        rc = dgcnn::conv_gemm(Ws, Cin, 2 * Cout, dP, (int64_t)2 * Cout * NODES, dX, dxgs, b,
+                              add ? dgcnn::EPI_ADD : dgcnn::EPI_PLAIN, false, st);
+        if (rc != PCD_OK) return rc;
+    }
+    return run_wgrad(dP, (int64_t)2 * Cout * NODES, 2 * Cout, X, xgs, Cin, b, wpart, dW, 1, st);
+}
+
+int run_reverse(const int32_t* lists, int kk, int32_t* rev_off, int32_t* rev, int64_t b, hipStream_t st) {
+    hipLaunchKernelGGL(reverse_lists_kernel, dim3((unsigned)b), dim3(64), 0, st, lists, kk, rev_off, rev);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+int run_pack(const float* W, int l, float* Wt, float* Ws, hipStream_t st) {
+    hipLaunchKernelGGL(pack_edge_kernel, dim3((unsigned)cdiv(kCin[l] * kCout[l], 256)), dim3(256), 0, st, W, kCin[l], kCout[l],
+                       Wt, Ws);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+struct TrainWs {             // byte offsets into the workspace
+    int64_t wt[6], ws[6], w7t, cat, P[6], arg, idx3, knn, rev_off, rev, Y7, arg7, dcat, dP, stat[7], sti[7], dstat, part,
+        wpart, flag, total;
+};
+TrainWs tlayout(int k, int emb, int64_t b) {
+    TrainWs w{};
+    int64_t o = 0;
+    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    for (int l = 0; l < 6; ++l) {
+        w.wt[l] = take((int64_t)2 * kCin[l] * kCout[l] * 4);
+        w.ws[l] = take((int64_t)2 * kCin[l] * kCout[l] * 4);
+    }
+    w.w7t = take((int64_t)1024 * emb * 4);
+    w.cat = take(b * 1024 * NODES * 4);
+    for (int l = 0; l < 6; ++l) w.P[l] = take(b * 2 * kCout[l] * NODES * 4);
+    w.arg = take(b * 1024 * NODES);
+    w.idx3 = take(b * NODES * 3 * 4);
+    w.knn = take(3 * b * NODES * k * 4);
+    w.rev_off = take(b * (NODES + 1) * 4);
+    w.rev = take(b * NODES * std::max(3, k) * 4);
+    w.Y7 = take(b * emb * NODES * 4);
+    w.arg7 = take(b * emb);
+    w.dcat = take(b * 1024 * NODES * 4);
+    w.dP = take(b * 512 * NODES * 4);
+    const int maxC = std::max(256, emb);
+    for (int l = 0; l < 7; ++l) {
+        const int C = l < 6 ? kCout[l] : emb;
+        w.stat[l] = take((int64_t)3 * C * 8);
+        w.sti[l] = take((int64_t)2 * C * 8);
+    }
+    w.dstat = take((int64_t)2 * maxC * 8);
+    w.part = take(cdiv(b, CHUNK) * maxC * 2 * 8);
+    w.wpart = take(wgrad_splits(b) * std::max<int64_t>((int64_t)emb * 1024, 512 * 256) * 4);
+    w.flag = take(4);
+    w.total = o;
+    return w;
+}
+
+int check_dims(int k, int emb, int64_t b) {
+    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
+    PCD_CHECK_ARG(emb >= 1 && emb <= (1 << 16), "emb_dims must be in [1, 65536]");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    return PCD_OK;
+}
+
+int check_ws(const TrainWs& w, const void* workspace, int64_t bytes) {
+    PCD_CHECK_ARG(workspace != nullptr && bytes >= w.total,
+                  "workspace of " + std::to_string(bytes) + " bytes is shorter than the " + std::to_string(w.total) +
+                      " that pcd_dgcnn_train_workspace_bytes asks for");
+    PCD_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+    return PCD_OK;
+}
+
+template <class T>
+T* at(void* ws, int64_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
+
+}  // namespace
+
+extern "C" {
+
+int pcd_dgcnn_train_workspace_bytes(int k, int emb_dims, int64_t b, int64_t* bytes) {
+    PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
+    const int rc = check_dims(k, emb_dims, b);
+    if (rc != PCD_OK) return rc;
+    *bytes = tlayout(k, emb_dims, b).total;
+    return PCD_OK;
+}
+
+int pcd_dgcnn_train_forward(const pcd_dgcnn_train_params* prm, int k, int emb_dims, const float* inputs, int64_t b,
+                            float* pooled, void* workspace, int64_t workspace_bytes, int32_t* lists_out, void* stream) {
+    PCD_CHECK_ARG(prm != nullptr, "params is null");
+    int rc = check_dims(k, emb_dims, b);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(b >= 1, "b must be >= 1 (batch statistics of an empty batch do not exist)");
+    PCD_CHECK_ARG(inputs != nullptr && pooled != nullptr, "inputs / pooled is null");
+    for (int l = 0; l < 7; ++l) {
+        const std::string name = std::to_string(l + 1);
+        PCD_CHECK_ARG(prm->conv_w[l] != nullptr, "conv" + name + " weight is null");
+        PCD_CHECK_ARG(prm->bn_weight[l] != nullptr && prm->bn_bias[l] != nullptr, "bn" + name + " weight / bias is null");
+        PCD_CHECK_ARG((prm->bn_mean[l] != nullptr) == (prm->bn_var[l] != nullptr),
+                      "bn" + name + ": running_mean and running_var go together");
+        PCD_CHECK_ARG(prm->bn_eps[l] >= 0.0, "bn" + name + " eps is invalid");
+        PCD_CHECK_ARG(prm->bn_momentum[l] >= 0.0 && prm->bn_momentum[l] <= 1.0, "bn" + name + " momentum must be in [0, 1]");
+    }
+    const TrainWs w = tlayout(k, emb_dims, b);
+    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    const int64_t cgs = 1024 * NODES;
+    float* cat = at<float>(workspace, w.cat);
+    int32_t* idx3 = at<int32_t>(workspace, w.idx3);
+    int32_t* knn = at<int32_t>(workspace, w.knn);
+    double* part = at<double>(workspace, w.part);
+    uint8_t* arg = at<uint8_t>(workspace, w.arg);
+    int* flag = at<int>(workspace, w.flag);
+
+    {   // the index columns first: a bad one ends the call before anything is computed or a buffer updated
+        int bad = kNoBadPatch;
+        PCD_HIP(hipMemsetAsync(flag, 0x7f, sizeof(int), st));
+        if ((rc = dgcnn::index_lists(inputs, b, idx3, flag, st)) != PCD_OK) return rc;
+        PCD_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        PCD_HIP(hipStreamSynchronize(st));
+        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
+                                          " has an index column (rows 17:20) outside [0, 63] or NaN; nothing written");
+    }
+    for (int l = 0; l < 6; ++l)
+        if ((rc = run_pack(prm->conv_w[l], l, at<float>(workspace, w.wt[l]), at<float>(workspace, w.ws[l]), st)) != PCD_OK)
+            return rc;
+    if ((rc = dgcnn::transpose(prm->conv_w[6], emb_dims, 1024, at<float>(workspace, w.w7t), st)) != PCD_OK) return rc;
+
+    auto bn_of = [&](int l) {
+        return Bn{prm->bn_weight[l], prm->bn_bias[l], prm->bn_mean[l], prm->bn_var[l], prm->bn_tracked[l], prm->bn_eps[l],
+                  prm->bn_momentum[l]};
+    };
+    for (int l = 0; l < 6; ++l) {
+        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
+        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
+        const int32_t* lists = idx3;
+        int kk = 3;
+        if (l >= 3) {
+            int32_t* mine = knn + (int64_t)(l - 3) * b * NODES * k;
+            if ((rc = dgcnn::knn(X, xgs, kCin[l], k, mine, b, st)) != PCD_OK) return rc;
+            lists = mine;
+            kk = k;
+        }
+        rc = edge_forward(l, at<float>(workspace, w.wt[l]), bn_of(l), X, xgs, lists, kk, at<float>(workspace, w.P[l]), part,
+                          at<double>(workspace, w.stat[l]), at<double>(workspace, w.sti[l]),
+                          cat + (int64_t)kCatOff[l] * NODES, cgs, arg + (int64_t)kCatOff[l] * NODES, cgs, b, st);
+        if (rc != PCD_OK) return rc;
+    }
+    {   // conv7: the product is stored (the backward turns it into dY in place), then statistics and pooling
+        float* Y7 = at<float>(workspace, w.Y7);
+        rc = dgcnn::conv_gemm(at<float>(workspace, w.w7t), emb_dims, 1024, cat, cgs, Y7, (int64_t)emb_dims * NODES, b,
+                              dgcnn::EPI_PLAIN, true, st);
+        if (rc != PCD_OK) return rc;
+        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
+        hipLaunchKernelGGL(row_stats_kernel, chunks, dim3(256), 0, st, Y7, emb_dims, b, part);
+        PCD_LAUNCH_CHECK();
+        rc = run_finalize(bn_of(6), part, b, emb_dims, (double)b * NODES, at<double>(workspace, w.stat[6]),
+                          at<double>(workspace, w.sti[6]), st);
+        if (rc != PCD_OK) return rc;
+        hipLaunchKernelGGL(pool_train_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, Y7, emb_dims,
+                           at<double>(workspace, w.sti[6]), pooled, at<uint8_t>(workspace, w.arg7));
+        PCD_LAUNCH_CHECK();
+    }
+    if (lists_out) PCD_HIP(hipMemcpyAsync(lists_out, knn, 3 * b * NODES * k * 4, hipMemcpyDeviceToDevice, st));
+    return PCD_OK;
+}
+
+int pcd_dgcnn_train_backward(int k, int emb_dims, const float* inputs, int64_t b, const float* d_pooled,
+                             const float* conv7_w, void* workspace, int64_t workspace_bytes,
+                             const pcd_dgcnn_train_grads* grads, void* stream) {
+    int rc = check_dims(k, emb_dims, b);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(b >= 1, "b must be >= 1");
+    PCD_CHECK_ARG(inputs != nullptr && d_pooled != nullptr && conv7_w != nullptr, "inputs / d_pooled / conv7_w is null");
+    PCD_CHECK_ARG(grads != nullptr, "grads is null");
+    for (int l = 0; l < 7; ++l)
+        PCD_CHECK_ARG(grads->conv_w[l] && grads->bn_weight[l] && grads->bn_bias[l],
+                      "gradient " + std::to_string(l + 1) + " has a null pointer");
+    const TrainWs w = tlayout(k, emb_dims, b);
+    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    const int64_t cgs = 1024 * NODES;
+    float* cat = at<float>(workspace, w.cat);
+    float* dcat = at<float>(workspace, w.dcat);
+    float* dP = at<float>(workspace, w.dP);
+    float* wpart = at<float>(workspace, w.wpart);
+    double* part = at<double>(workspace, w.part);
+    double* dstat = at<double>(workspace, w.dstat);
+    int32_t* idx3 = at<int32_t>(workspace, w.idx3);
+    int32_t* knn = at<int32_t>(workspace, w.knn);
+    int32_t* rev_off = at<int32_t>(workspace, w.rev_off);
+    int32_t* rev = at<int32_t>(workspace, w.rev);
+    const uint8_t* arg = at<uint8_t>(workspace, w.arg);
+    {   // conv7: pooling, LeakyReLU and batch norm, dY in place of the stored product
+        float* Y7 = at<float>(workspace, w.Y7);
+        const uint8_t* arg7 = at<uint8_t>(workspace, w.arg7);
+        const double* stat = at<double>(workspace, w.stat[6]);
+        const double* sti = at<double>(workspace, w.sti[6]);
+        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
+        hipLaunchKernelGGL(pool_bwd_reduce_kernel, chunks, dim3(256), 0, st, Y7, emb_dims, arg7, d_pooled, stat, sti, b, part);
+        PCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(emb_dims, 64)), dim3(64), 0, st, part,
+                           (int)cdiv(b, CHUNK), emb_dims, dstat, grads->bn_weight[6], grads->bn_bias[6]);
+        PCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pool_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, Y7,
+                           emb_dims, arg7, d_pooled, stat, sti, dstat, 1.0 / ((double)b * NODES));
+        PCD_LAUNCH_CHECK();
+        // dcat = W7^T dY: W7 [emb][1024] itself is the GEMM's transposed operand; every slice's first contribution
+        rc = dgcnn::conv_gemm(conv7_w, 1024, emb_dims, Y7, (int64_t)emb_dims * NODES, dcat, cgs, b, dgcnn::EPI_PLAIN, false, st);
+        if (rc != PCD_OK) return rc;
+        rc = run_wgrad(Y7, (int64_t)emb_dims * NODES, emb_dims, cat, cgs, 1024, b, wpart, grads->conv_w[6], 0, st);
+        if (rc != PCD_OK) return rc;
+    }
+    for (int l = 5; l >= 0; --l) {
+        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
+        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
+        const int32_t* lists = l >= 3 ? knn + (int64_t)(l - 3) * b * NODES * k : idx3;
+        const int kk = l >= 3 ? k : 3;
+        if (l >= 2 && (rc = run_reverse(lists, kk, rev_off, rev, b, st)) != PCD_OK) return rc;   // layers 1-3 share theirs
+        // the layer's input slice already holds conv7's contribution: this layer's is added second
+        float* dX = l == 0 ? nullptr : dcat + (int64_t)kCatOff[l - 1] * NODES;
+        rc = edge_backward(l, at<float>(workspace, w.ws[l]), X, xgs, lists, kk, rev_off, rev, at<float>(workspace, w.P[l]),
+                           arg + (int64_t)kCatOff[l] * NODES, cgs, dcat + (int64_t)kCatOff[l] * NODES, cgs,
+                           at<double>(workspace, w.stat[l]), at<double>(workspace, w.sti[l]), part, dstat, dP, wpart,
+                           grads->bn_weight[l], grads->bn_bias[l], grads->conv_w[l], dX, cgs, true, b, st);
+        if (rc != PCD_OK) return rc;
+    }
+    return PCD_OK;
+}
+
+int pcd_dgcnn_wgrad_split(int64_t b, int64_t* patches_per_split) {
+    PCD_CHECK_ARG(patches_per_split != nullptr, "patches_per_split is null");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    *patches_per_split = wgrad_pps(b);
+    return PCD_OK;
+}
+
+int pcd_dgcnn_wgrad(const float* dy, const float* x, int m_rows, int k_cols, int64_t b, float* dw, void* stream) {
+    PCD_CHECK_ARG(m_rows >= 1 && k_cols >= 1, "M and K must be >= 1");
+    PCD_CHECK_ARG(m_rows <= (1 << 16) && k_cols <= (1 << 16), "M and K must be <= 65536");
+    PCD_CHECK_ARG(b >= 1 && b <= kMaxBatch, "b must be in [1, 2^20]");
+    PCD_CHECK_ARG(dy != nullptr && x != nullptr && dw != nullptr, "dy / x / dw is null");
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    float* part;
+    PCD_HIP(tmp.alloc(&part, wgrad_splits(b) * (int64_t)m_rows * k_cols * sizeof(float)));
+    const int rc = run_wgrad(dy, (int64_t)m_rows * NODES, m_rows, x, (int64_t)k_cols * NODES, k_cols, b, part, dw, 0, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+// the edge stage's scratch: one allocation, carved
+namespace {
+struct StageWs {
+    int64_t wt, ws, P, part, sti, stat, dstat, rev_off, rev, dP, wpart, arg, total;
+};
+StageWs slayout(int l, int n, int64_t b) {
+    StageWs w{};
+    int64_t o = 0;
+    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    const int Cin = kCin[l], Cout = kCout[l];
+    w.wt = take((int64_t)2 * Cin * Cout * 4);
+    w.ws = take((int64_t)2 * Cin * Cout * 4);
+    w.P = take(b * 2 * Cout * NODES * 4);
+    w.part = take(cdiv(b, CHUNK) * Cout * 2 * 8);
+    w.sti = take((int64_t)2 * Cout * 8);
+    w.stat = take((int64_t)3 * Cout * 8);
+    w.dstat = take((int64_t)2 * Cout * 8);
+    w.rev_off = take(b * (NODES + 1) * 4);
+    w.rev = take(b * NODES * n * 4);
+    w.dP = take(b * 2 * Cout * NODES * 4);
+    w.wpart = take(wgrad_splits(b) * (int64_t)2 * Cout * Cin * 4);
+    w.arg = take(b * Cout * NODES);
+    w.total = o;
+    return w;
+}
+int check_stage(int layer, int64_t b, int n) {
+    PCD_CHECK_ARG(layer >= 1 && layer <= 6, "layer must be in [1, 6]");
+    PCD_CHECK_ARG(b >= 1 && b <= kMaxBatch, "b must be in [1, 2^20]");
+    PCD_CHECK_ARG(n >= 1 && n <= NODES, "list_len must be in [1, 64]");
+    return PCD_OK;
+}
+}  // namespace
+
+int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* beta, double eps, double momentum,
+                             float* running_mean, float* running_var, int64_t* tracked, int layer, const float* x,
+                             int64_t b, const int32_t* lists, int list_len, float* out, uint8_t* argmax, double* stats,
+                             void* stream) {
+    int rc = check_stage(layer, b, list_len);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(w && gamma && beta && x && lists && out && argmax && stats, "a pointer is null");
+    PCD_CHECK_ARG((running_mean != nullptr) == (running_var != nullptr), "running_mean and running_var go together");
+    PCD_CHECK_ARG(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, "eps / momentum is invalid");
+    const int l = layer - 1, Cout = kCout[l];
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    const StageWs s = slayout(l, list_len, b);
+    char* ws;
+    PCD_HIP(tmp.alloc(&ws, s.total));
+    if ((rc = run_pack(w, l, at<float>(ws, s.wt), at<float>(ws, s.ws), st)) != PCD_OK) return rc;
+    const Bn bn{gamma, beta, running_mean, running_var, tracked, eps, momentum};
+    rc = edge_forward(l, at<float>(ws, s.wt), bn, x, (int64_t)kCin[l] * NODES, lists, list_len, at<float>(ws, s.P),
+                      at<double>(ws, s.part), stats, at<double>(ws, s.sti), out, (int64_t)Cout * NODES, argmax,
+                      (int64_t)Cout * NODES, b, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+int pcd_dgcnn_edgeconv_train_backward(const float* w, const float* gamma, const float* beta, double eps, int layer,
+                                      const float* x, int64_t b, const int32_t* lists, int list_len, const float* g,
+                                      float* dab, float* dgamma, float* dbeta, float* dw, float* dx, void* stream) {
+    int rc = check_stage(layer, b, list_len);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(w && gamma && beta && x && lists && g && dab && dgamma && dbeta && dw, "a pointer is null");
+    PCD_CHECK_ARG(eps >= 0.0, "eps is invalid");
+    const int l = layer - 1, Cin = kCin[l], Cout = kCout[l];
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    const StageWs s = slayout(l, list_len, b);
+    char* ws;
+    PCD_HIP(tmp.alloc(&ws, s.total + (int64_t)b * Cout * NODES * 4));
+    float* out = at<float>(ws, s.total);
+    if ((rc = run_pack(w, l, at<float>(ws, s.wt), at<float>(ws, s.ws), st)) != PCD_OK) return rc;
+    const Bn bn{gamma, beta, nullptr, nullptr, nullptr, eps, 0.0};
+    // the forward again (no buffer is touched), then the backward on what it left
+    rc = edge_forward(l, at<float>(ws, s.wt), bn, x, (int64_t)Cin * NODES, lists, list_len, at<float>(ws, s.P),
+                      at<double>(ws, s.part), at<double>(ws, s.stat), at<double>(ws, s.sti), out, (int64_t)Cout * NODES,
+                      at<uint8_t>(ws, s.arg), (int64_t)Cout * NODES, b, st);
+    if (rc != PCD_OK) return rc;
+    if ((rc = run_reverse(lists, list_len, at<int32_t>(ws, s.rev_off), at<int32_t>(ws, s.rev), b, st)) != PCD_OK) return rc;
+    rc = edge_backward(l, at<float>(ws, s.ws), x, (int64_t)Cin * NODES, lists, list_len, at<int32_t>(ws, s.rev_off),
+                       at<int32_t>(ws, s.rev), at<float>(ws, s.P), at<uint8_t>(ws, s.arg), (int64_t)Cout * NODES, g,
+                       (int64_t)Cout * NODES, at<double>(ws, s.stat), at<double>(ws, s.sti), at<double>(ws, s.part),
+                       at<double>(ws, s.dstat), dab, at<float>(ws, s.wpart), dgamma, dbeta, dw, dx, (int64_t)Cin * NODES,
+                       false, b, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+}  // extern "C"

@@ -64,6 +64,18 @@ class DgcnnDebug(ctypes.Structure):
                 ("h3", c_void_p)]
 
 
+class DgcnnTrainParams(ctypes.Structure):
+    """Mirror of ``pcd_dgcnn_train_params`` (include/pcd.h)."""
+    _fields_ = [("conv_w", c_void_p * 7), ("bn_weight", c_void_p * 7), ("bn_bias", c_void_p * 7),
+                ("bn_mean", c_void_p * 7), ("bn_var", c_void_p * 7), ("bn_tracked", c_void_p * 7),
+                ("bn_eps", c_double * 7), ("bn_momentum", c_double * 7)]
+
+
+class DgcnnTrainGrads(ctypes.Structure):
+    """Mirror of ``pcd_dgcnn_train_grads`` (include/pcd.h)."""
+    _fields_ = [("conv_w", c_void_p * 7), ("bn_weight", c_void_p * 7), ("bn_bias", c_void_p * 7)]
+
+
 # name -> (restype, argtypes); the exact export list of include/pcd.h
 _SIGS = {
     "pcd_last_error": (ctypes.c_char_p, []),
@@ -177,6 +189,19 @@ _SIGS = {
     "pcd_dgcnn_edgeconv": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pcd_dgcnn_gemm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "pcd_dgcnn_train_workspace_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_int64)]),
+    "pcd_dgcnn_train_forward": (c_int, [POINTER(DgcnnTrainParams), c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_int64, c_void_p, c_void_p]),
+    "pcd_dgcnn_train_backward": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         POINTER(DgcnnTrainGrads), c_void_p]),
+    "pcd_dgcnn_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "pcd_dgcnn_wgrad_split": (c_int, [c_int64, POINTER(c_int64)]),
+    "pcd_dgcnn_edgeconv_train": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "pcd_dgcnn_edgeconv_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64,
+                                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p]),
     "pcd_orient_normals_mst": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
     "pcd_orient_normals_mst_gpu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "pcd_host_eigh3": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1105,7 +1130,8 @@ def orient_normals_mst_gpu(pos, n, a, b) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------------- DGCNN forward
 DGCNN_CIN = (17, 64, 64, 128, 256, 256)
 DGCNN_COUT = (64, 64, 128, 256, 256, 256)
-EPI_PLAIN, EPI_AFFINE_LRELU, EPI_POOL, EPI_AFFINE = range(4)
+EPI_PLAIN, EPI_AFFINE_LRELU, EPI_POOL, EPI_AFFINE, EPI_ADD = range(5)
+host_packs = 0                       # how often Dgcnn() packed a model's weights through the host (pcd_dgcnn_create)
 DGCNN_NO_BAD_PATCH = 0x7f7f7f7f      # PCD_DGCNN_NO_BAD_PATCH
 
 
@@ -1142,6 +1168,8 @@ class Dgcnn:
                 raise ValueError(f"pcd: linear{i + 1}: weight must be [out, in] and the bias [out]")
             w.lin_w[i], w.lin_rows[i], w.lin_cols[i] = p32(lw), lw.shape[0], lw.shape[1]
             w.lin_b[i] = None if lb is None else p32(lb)
+        global host_packs
+        host_packs += 1
         h = c_void_p()
         device()
         check(lib().pcd_dgcnn_create(ctypes.byref(w), int(k), int(init_dims), int(emb_dims), int(output_channels),
@@ -1227,9 +1255,10 @@ def dgcnn_knn(x: torch.Tensor, k: int) -> torch.Tensor:
     return lists
 
 
-def dgcnn_gemm(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=None, t=None) -> torch.Tensor:
+def dgcnn_gemm(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=None, t=None, y=None) -> torch.Tensor:
     """w [M, K] . x on the network's MFMA GEMM (pcd_dgcnn_gemm): x [b, K, 64] -> [b, M, 64] ([b, 2 M] with the
-    pooling epilogue), or x [K, b] -> [M, b]."""
+    pooling epilogue), or x [K, b] -> [M, b].  EPI_ADD adds the product into y (float32, contiguous, on the device)
+    and returns it."""
     w, x = f32(w), f32(x)
     M, K = w.shape
     if x.dim() == 3:
@@ -1244,7 +1273,167 @@ def dgcnn_gemm(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=No
         shape = (M, b)
     s = None if s is None else f32(s)
     t = None if t is None else f32(t)
-    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if epilogue == EPI_ADD:
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.device != x.device \
+                or tuple(y.shape) != shape or not y.is_contiguous():
+            raise ValueError(f"pcd: dgcnn_gemm: EPI_ADD needs y float32 {shape} contiguous on {x.device}")
+    elif y is not None:
+        raise ValueError("pcd: dgcnn_gemm: y is taken by EPI_ADD only")
+    else:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
     check(lib().pcd_dgcnn_gemm(ptr(w), ptr(x), M, K, b, nodes, int(epilogue), ptr(s), ptr(t), ptr(y),
                                c_void_p(stream_ptr())), "pcd_dgcnn_gemm")
     return y
+
+
+# ----------------------------------------------------------------------------------------------- DGCNN training
+def dgcnn_train_workspace_bytes(k: int, emb_dims: int, b: int) -> int:
+    v = c_int64(0)
+    check(lib().pcd_dgcnn_train_workspace_bytes(int(k), int(emb_dims), int(b), ctypes.byref(v)),
+          "pcd_dgcnn_train_workspace_bytes")
+    return v.value
+
+
+def _train_tensor(t, what, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"pcd: DGCNN training: {what} must be a contiguous {dtype} tensor on the HIP device")
+    return t.data_ptr()
+
+
+def _train_workspace(ws, dev):
+    if not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous():
+        raise ValueError(f"pcd: DGCNN training workspace must be a contiguous tensor on {dev}, got "
+                         f"{getattr(ws, 'device', type(ws).__name__)}")
+    return ws.numel() * ws.element_size()
+
+
+def dgcnn_train_forward(conv, bn, k: int, emb_dims: int, inputs: torch.Tensor, workspace: torch.Tensor,
+                        want_lists: bool = False):
+    """conv1-7 and the pooling in train() (pcd_dgcnn_train_forward).  conv: 7 weights [out, 2 in(, 1, 1)]; bn: 7 tuples
+    (weight, bias, running_mean, running_var, num_batches_tracked, eps, momentum) whose buffers (None: none) are
+    updated in place -- all float32 (the counter int64), contiguous, on the device: nothing is copied.  inputs
+    [b, 20, 64] float32 -> pooled [b, 2 emb]; with want_lists also the lists of layers 4-6, int32 [3, b, 64, k].  The
+    workspace (dgcnn_train_workspace_bytes) carries the forward's state to dgcnn_train_backward."""
+    if len(conv) != 7 or len(bn) != 7:
+        raise ValueError("pcd: DGCNN training takes 7 convolution weights and 7 batch norms")
+    x = inputs
+    _train_tensor(x, "inputs")
+    if x.dim() != 3 or x.size(1) != 20 or x.size(2) != 64:
+        raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(x.shape)}")
+    b, dev = x.size(0), x.device
+    prm = DgcnnTrainParams()
+    rows = [c for _, c in ((17, 64), (64, 64), (64, 128), (128, 256), (256, 256), (256, 256))] + [int(emb_dims)]
+    cols = [34, 128, 128, 256, 512, 512, 1024]
+    for i, cw in enumerate(conv):
+        if cw.numel() != rows[i] * cols[i] or cw.shape[0] != rows[i]:
+            raise ValueError(f"pcd: conv{i + 1} weight must be [{rows[i]}, {cols[i]}], got {tuple(cw.shape)}")
+        prm.conv_w[i] = _train_tensor(cw, f"conv{i + 1} weight")
+    for i, (g, be, mu, var, nbt, eps, mom) in enumerate(bn):
+        if mom is None:
+            raise ValueError(f"pcd: bn{i + 1}: momentum=None (a cumulative average) is not supported in training")
+        for t, what in ((g, "weight"), (be, "bias"), (mu, "running_mean"), (var, "running_var")):
+            if t is not None and t.numel() != rows[i]:
+                raise ValueError(f"pcd: bn{i + 1}.{what} must have {rows[i]} channels")
+        prm.bn_weight[i], prm.bn_bias[i] = _train_tensor(g, f"bn{i + 1}.weight"), _train_tensor(be, f"bn{i + 1}.bias")
+        prm.bn_mean[i] = None if mu is None else _train_tensor(mu, f"bn{i + 1}.running_mean")
+        prm.bn_var[i] = None if var is None else _train_tensor(var, f"bn{i + 1}.running_var")
+        prm.bn_tracked[i] = None if nbt is None else _train_tensor(nbt, f"bn{i + 1}.num_batches_tracked", torch.int64)
+        prm.bn_eps[i], prm.bn_momentum[i] = float(eps), float(mom)
+    nbytes = _train_workspace(workspace, dev)
+    pooled = torch.empty((b, 2 * int(emb_dims)), dtype=torch.float32, device=dev)
+    lists = torch.empty((3, b, 64, int(k)), dtype=torch.int32, device=dev) if want_lists else None
+    check(lib().pcd_dgcnn_train_forward(ctypes.byref(prm), int(k), int(emb_dims), ptr(x), b, ptr(pooled), ptr(workspace),
+                                        nbytes, ptr(lists), c_void_p(stream_ptr())), "pcd_dgcnn_train_forward")
+    return (pooled, lists) if want_lists else pooled
+
+
+def dgcnn_train_backward(conv, k: int, emb_dims: int, inputs: torch.Tensor, d_pooled: torch.Tensor,
+                         workspace: torch.Tensor):
+    """d_pooled [b, 2 emb] -> (7 conv weight gradients shaped like conv, 7 bn weight gradients, 7 bn bias gradients)
+    from the workspace dgcnn_train_forward left (pcd_dgcnn_train_backward).  One backward per forward."""
+    x = inputs
+    _train_tensor(x, "inputs")
+    b, dev = x.size(0), x.device
+    dp = f32(d_pooled)
+    if tuple(dp.shape) != (b, 2 * int(emb_dims)):
+        raise ValueError(f"pcd: d_pooled must be [{b}, {2 * int(emb_dims)}], got {tuple(dp.shape)}")
+    g = DgcnnTrainGrads()
+    dw = [torch.empty_like(cw, memory_format=torch.contiguous_format) for cw in conv]
+    dg = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
+    db = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
+    for i in range(7):
+        g.conv_w[i], g.bn_weight[i], g.bn_bias[i] = dw[i].data_ptr(), dg[i].data_ptr(), db[i].data_ptr()
+    check(lib().pcd_dgcnn_train_backward(int(k), int(emb_dims), ptr(x), b, ptr(dp), c_void_p(_train_tensor(conv[6], "conv7 weight")),
+                                         ptr(workspace), _train_workspace(workspace, dev), ctypes.byref(g),
+                                         c_void_p(stream_ptr())), "pcd_dgcnn_train_backward")
+    return dw, dg, db
+
+
+def dgcnn_wgrad_split(b: int) -> int:
+    """Patches per run of the weight gradient's split reduction (pcd_dgcnn_wgrad_split)."""
+    v = c_int64(0)
+    check(lib().pcd_dgcnn_wgrad_split(int(b), ctypes.byref(v)), "pcd_dgcnn_wgrad_split")
+    return v.value
+
+
+def dgcnn_wgrad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """dy [b, M, 64], x [b, K, 64] -> dw [M, K] = sum over the b x 64 columns of dy x^T (pcd_dgcnn_wgrad)."""
+    dy, x = f32(dy), f32(x)
+    if dy.dim() != 3 or x.dim() != 3 or dy.size(0) != x.size(0) or dy.size(2) != 64 or x.size(2) != 64:
+        raise ValueError(f"pcd: dgcnn_wgrad: dy {tuple(dy.shape)} / x {tuple(x.shape)} do not fit")
+    dw = torch.empty((dy.size(1), x.size(1)), dtype=torch.float32, device=x.device)
+    check(lib().pcd_dgcnn_wgrad(ptr(dy), ptr(x), dy.size(1), x.size(1), x.size(0), ptr(dw), c_void_p(stream_ptr())),
+          "pcd_dgcnn_wgrad")
+    return dw
+
+
+def _edge_train_args(layer, w, x, lists):
+    if not 1 <= int(layer) <= 6:
+        raise ValueError("pcd: DGCNN edge layers are 1-6")
+    cin, cout = DGCNN_CIN[layer - 1], DGCNN_COUT[layer - 1]
+    w, x, lists = f32(w).reshape(w.shape[0], -1), f32(x), on_device(lists, torch.int32)
+    b = x.size(0)
+    if tuple(w.shape) != (cout, 2 * cin) or tuple(x.shape) != (b, cin, 64) or lists.dim() != 3 \
+            or tuple(lists.shape[:2]) != (b, 64):
+        raise ValueError(f"pcd: edgeconv_train layer {layer}: w {tuple(w.shape)} / x {tuple(x.shape)} / lists "
+                         f"{tuple(lists.shape)} do not fit")
+    return w, x, lists, b, cin, cout
+
+
+def dgcnn_edgeconv_train(layer: int, w, gamma, beta, eps: float, x, lists, momentum: float = 0.1, running_mean=None,
+                         running_var=None, tracked=None):
+    """One edge layer in train() with injected lists (pcd_dgcnn_edgeconv_train): (out [b, Cout, 64], argmax uint8
+    [b, Cout, 64], stats float64 [3, Cout] = mean, biased variance, 1 / sqrt(var + eps)).  The running buffers
+    (float32 / int64, contiguous, on the device), when given, are updated in place."""
+    w, x, lists, b, cin, cout = _edge_train_args(layer, w, x, lists)
+    gamma, beta = f32(gamma), f32(beta)
+    bufs = [None if t is None else _train_tensor(t, what, dt) for t, what, dt in
+            ((running_mean, "running_mean", torch.float32), (running_var, "running_var", torch.float32),
+             (tracked, "num_batches_tracked", torch.int64))]
+    out = torch.empty((b, cout, 64), dtype=torch.float32, device=x.device)
+    arg = torch.empty((b, cout, 64), dtype=torch.uint8, device=x.device)
+    stats = torch.empty((3, cout), dtype=torch.float64, device=x.device)
+    check(lib().pcd_dgcnn_edgeconv_train(ptr(w), ptr(gamma), ptr(beta), float(eps), float(momentum), bufs[0], bufs[1],
+                                         bufs[2], int(layer), ptr(x), b, ptr(lists), lists.size(2), ptr(out), ptr(arg),
+                                         ptr(stats), c_void_p(stream_ptr())), "pcd_dgcnn_edgeconv_train")
+    return out, arg, stats
+
+
+def dgcnn_edgeconv_train_backward(layer: int, w, gamma, beta, eps: float, x, lists, g, want_dx: bool = True):
+    """The backward of dgcnn_edgeconv_train for g = dL/d out [b, Cout, 64] (pcd_dgcnn_edgeconv_train_backward):
+    {"dab" [b, 2 Cout, 64], "dgamma", "dbeta" [Cout], "dw" [Cout, 2 Cin], "dx" [b, Cin, 64]}."""
+    w, x, lists, b, cin, cout = _edge_train_args(layer, w, x, lists)
+    gamma, beta, g = f32(gamma), f32(beta), f32(g)
+    if tuple(g.shape) != (b, cout, 64):
+        raise ValueError(f"pcd: edgeconv_train_backward: g must be [{b}, {cout}, 64], got {tuple(g.shape)}")
+    dev = x.device
+    r = {"dab": torch.empty((b, 2 * cout, 64), dtype=torch.float32, device=dev),
+         "dgamma": torch.empty(cout, dtype=torch.float32, device=dev),
+         "dbeta": torch.empty(cout, dtype=torch.float32, device=dev),
+         "dw": torch.empty((cout, 2 * cin), dtype=torch.float32, device=dev),
+         "dx": torch.empty((b, cin, 64), dtype=torch.float32, device=dev) if want_dx else None}
+    check(lib().pcd_dgcnn_edgeconv_train_backward(ptr(w), ptr(gamma), ptr(beta), float(eps), int(layer), ptr(x), b,
+                                                  ptr(lists), lists.size(2), ptr(g), ptr(r["dab"]), ptr(r["dgamma"]),
+                                                  ptr(r["dbeta"]), ptr(r["dw"]), ptr(r["dx"]), c_void_p(stream_ptr())),
+          "pcd_dgcnn_edgeconv_train_backward")
+    return r
