@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 import pcd_native as _nat
 
-_EDGE = ((17, 64), (64, 64), (64, 128), (128, 256), (256, 256), (256, 256))   # (in, out) of conv1-6
+_EDGE = tuple(zip(_nat.DGCNN_CIN, _nat.DGCNN_COUT))   # (in, out) of conv1-6
 _HEAD = (512, 256, 64)
 
 
@@ -119,6 +119,13 @@ class DGCNN(nn.Module):
             self._packed = (key, native)
         return self._packed[1]
 
+    @staticmethod
+    def _check_inputs(inputs):
+        if not isinstance(inputs, torch.Tensor) or not inputs.is_cuda:
+            raise ValueError("DGCNN: inputs must be a tensor on the HIP device (there is no CPU path)")
+        if inputs.dim() != 3 or inputs.size(1) != 20 or inputs.size(2) != 64:
+            raise ValueError(f"DGCNN: inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
+
     def forward(self, inputs, workspace=None, debug=False, first_bad=None, patch_base=0):
         """inputs [b, 20, 64] on the device (float64 is cast to float32) -> [b, output_channels] float32.
         workspace: an optional uint8 device tensor of at least native().workspace_bytes(b) bytes to reuse between
@@ -133,10 +140,7 @@ class DGCNN(nn.Module):
             if workspace is not None or first_bad is not None or patch_base != 0:
                 raise ValueError("DGCNN: workspace / first_bad / patch_base belong to eval(); train() owns its workspace")
             return self._train_forward(inputs, debug)
-        if not isinstance(inputs, torch.Tensor) or not inputs.is_cuda:
-            raise ValueError("DGCNN: inputs must be a tensor on the HIP device (there is no CPU path)")
-        if inputs.dim() != 3 or inputs.size(1) != 20 or inputs.size(2) != 64:
-            raise ValueError(f"DGCNN: inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
+        self._check_inputs(inputs)
         with torch.no_grad():
             return self._native().forward(inputs.to(torch.float32), workspace, debug, first_bad, patch_base)
 
@@ -148,10 +152,7 @@ class DGCNN(nn.Module):
     def _train_forward(self, inputs, debug):
         """train() of a trainable model: [b, 20, 64] float32 -> [b, output_channels] with a grad_fn.  debug=True also
         returns {"lists" int32 [3, b, 64, k], "pooled" [b, 2 emb]}."""
-        if not isinstance(inputs, torch.Tensor) or not inputs.is_cuda:
-            raise ValueError("DGCNN: inputs must be a tensor on the HIP device (there is no CPU path)")
-        if inputs.dim() != 3 or inputs.size(1) != 20 or inputs.size(2) != 64:
-            raise ValueError(f"DGCNN: inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
+        self._check_inputs(inputs)
         if inputs.requires_grad:
             raise ValueError("DGCNN: there is no gradient with respect to the inputs (inputs.requires_grad is set)")
         if inputs.size(0) < 1:

@@ -16,6 +16,8 @@
 // Every output element depends on its own patch only and is summed in a fixed order: a patch's output bits do not
 // depend on the batch, its place in it, or the run.  No float atomics.  The library's -ffp-contract=off stays; where a
 // fused multiply-add is meant the code says fmaf (or is the MFMA).
+// The layer table, an edge layer's wiring (edge_layer) and the workspace carver are in pcd_dgcnn.h, shared with
+// csrc/dgcnn_train.hip, which also launches this file's GEMM, k-NN, index and transpose kernels through pcd::dgcnn.
 #include <limits.h>
 #include <math.h>
 
@@ -25,20 +27,13 @@
 #include "pcd_host.h"
 
 using namespace pcd;
+using namespace pcd::dgcnn;
 
 namespace {
 
-constexpr int NODES = 64;            // rows of a patch
 constexpr int BM = 128, BN = 64, BK = 32;
 // LDS row strides (floats) of the W and X tiles: = 32 mod 64, so the two k rows an MFMA reads fall in different bank halves
 constexpr int LDA = 160, LDB = 96;
-using dgcnn::EPI_PLAIN;
-using dgcnn::EPI_AFFINE_LRELU;
-using dgcnn::EPI_POOL;
-using dgcnn::EPI_AFFINE;
-using dgcnn::EPI_ADD;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GemmArgs {
     const float* Wt;        // [K][M]: the weight, transposed (rows are contiguous in m)
@@ -52,7 +47,6 @@ struct GemmArgs {
     int M, K, epi;
 };
 
-__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
 // max that keeps a NaN (torch's max does)
 __device__ __forceinline__ float nanmax(float a, float b) { return (b > a || b != b) ? b : a; }
 
@@ -135,7 +129,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             acc[1][r] = (float)wide[1][r];
         }
     }
-    // C layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int cn = wn + acol;
     const int64_t n = n0 + cn;
     float* Ps = lds;                                   // EPI_POOL: [BM][65] staging (every wave is past the k loop)
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rm = wm + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * arow;
+            const int rm = mfma_row(wm + 32 * h, r, arow);
             const int m = m0 + rm;
             float v = acc[h][r];
             if (a.epi != EPI_PLAIN && a.epi != EPI_ADD && m < a.M) {
@@ -273,11 +266,6 @@ __global__ __launch_bounds__(256) void edge_kernel(const float* P, int Cout, con
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-const int kCin[6] = {17, 64, 64, 128, 256, 256};
-const int kCout[6] = {64, 64, 128, 256, 256, 256};
-const int kCatOff[6] = {0, 64, 128, 256, 512, 768};   // the layer's slice of the [1024][64] concatenation
-const int kHead[3] = {512, 256, 64};
-
 constexpr int kWideFlush = 8;        // k per float32 chain of the train-mode forward products
 
 int launch_gemm(const GemmArgs& a, hipStream_t st, bool wide = false) {
@@ -321,48 +309,37 @@ struct pcd_dgcnn {
 namespace {
 
 struct Workspace {
-    int64_t cat, P, idx3, knn, pooled, h1, h2, h3, flag, total;   // byte offsets
+    float *cat, *P, *pooled, *h[3];   // [b][1024][64], [b][512][64], [2 emb][b], linear1-3's [kHead][b]
+    int32_t *idx3, *knn, *flag;       // [b][64][3], [3][b][64][k], [1]
+    int64_t total;                    // bytes
 };
-Workspace layout(const pcd_dgcnn* m, int64_t b) {
+Workspace layout(const pcd_dgcnn* m, int64_t b, void* ws) {
     Workspace w{};
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    w.cat = take(b * 1024 * NODES * 4);
-    w.P = take(b * 512 * NODES * 4);
-    w.idx3 = take(b * NODES * 3 * 4);
-    w.knn = take(3 * b * NODES * m->k * 4);
-    w.pooled = take(2 * (int64_t)m->emb * b * 4);
-    w.h1 = take(512 * b * 4);
-    w.h2 = take(256 * b * 4);
-    w.h3 = take(64 * b * 4);
-    w.flag = take(4);
-    w.total = o;
+    Carver c{ws};
+    w.cat = c.carve<float>(b * 1024 * NODES * 4);
+    w.P = c.carve<float>(b * 512 * NODES * 4);
+    w.idx3 = c.carve<int32_t>(b * NODES * 3 * 4);
+    w.knn = c.carve<int32_t>(3 * b * NODES * m->k * 4);
+    w.pooled = c.carve<float>(2 * (int64_t)m->emb * b * 4);
+    for (int l = 0; l < 3; ++l) w.h[l] = c.carve<float>(kHead[l] * b * 4);
+    w.flag = c.carve<int32_t>(4);
+    w.total = c.used;
     return w;
 }
 
-int run_edge(const pcd_dgcnn* m, int layer, const float* X, int64_t xgs, const int32_t* lists, int kk, float* P,
-             float* out, int64_t ogs, int64_t b, hipStream_t st) {
-    const int Cin = kCin[layer], Cout = kCout[layer];
-    const int rc = launch_gemm(conv_args(m->wt[layer], 2 * Cout, Cin, X, xgs, P, (int64_t)2 * Cout * NODES, b), st);
+// out: the layer's output [b][Cout][64], patch stride e.ogs
+int run_edge(const pcd_dgcnn* m, int layer, const EdgeLayer& e, float* P, float* out, int64_t b, hipStream_t st) {
+    const int rc = launch_gemm(conv_args(m->wt[layer], 2 * e.Cout, e.Cin, e.X, e.xgs, P, (int64_t)2 * e.Cout * NODES, b), st);
     if (rc != PCD_OK) return rc;
-    hipLaunchKernelGGL(edge_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
-                       m->s[layer], m->t[layer], out, ogs);
+    hipLaunchKernelGGL(edge_kernel, dim3((unsigned)b, (unsigned)cdiv(e.Cout, 4)), dim3(256), 0, st, P, e.Cout, e.lists,
+                       e.kk, m->s[layer], m->t[layer], out, e.ogs);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
-
-int run_knn(const float* x, int64_t xgs, int C, int k, int32_t* lists, int64_t b, hipStream_t st) {
-    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)b), dim3(256), 0, st, x, xgs, C, k, lists);
-    PCD_LAUNCH_CHECK();
-    return PCD_OK;
-}
-
-constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
-constexpr int64_t kMaxBatch = 1 << 20;   // 2^31 / (64 x 20) patches and more would pass int32 in the index flag
 
 }  // namespace
 
-// what csrc/dgcnn_train.hip shares with the forward (pcd_dgcnn.h)
+// the launchers csrc/dgcnn_train.hip uses too (declared in pcd_dgcnn.h)
 namespace pcd {
 namespace dgcnn {
 
@@ -374,12 +351,25 @@ int conv_gemm(const float* Wt, int M, int K, const float* X, int64_t xgs, float*
 }
 
 int knn(const float* x, int64_t xgs, int C, int k, int32_t* lists, int64_t b, hipStream_t st) {
-    return run_knn(x, xgs, C, k, lists, b, st);
+    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)b), dim3(256), 0, st, x, xgs, C, k, lists);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
 }
 
-int index_lists(const float* inputs, int64_t b, int32_t* lists, int* flag, hipStream_t st) {
-    hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, lists, flag, 0);
+int index_lists(const float* inputs, int64_t b, int32_t* lists, int* flag, int patch_base, hipStream_t st) {
+    hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, lists, flag,
+                       patch_base);
     PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+
+int index_lists_checked(const float* inputs, int64_t b, int32_t* lists, int* flag, int* bad, hipStream_t st) {
+    *bad = kNoBadPatch;
+    PCD_HIP(hipMemsetAsync(flag, 0x7f, sizeof(int), st));
+    const int rc = index_lists(inputs, b, lists, flag, 0, st);
+    if (rc != PCD_OK) return rc;
+    PCD_HIP(hipMemcpyAsync(bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    PCD_HIP(hipStreamSynchronize(st));
     return PCD_OK;
 }
 
@@ -407,9 +397,8 @@ int pcd_dgcnn_create(const pcd_dgcnn_weights* w, int k, int init_dims, int emb_d
     int cr[7], cc[7], bl[10], lr[4], lc[4];
     for (int l = 0; l < 6; ++l) { cr[l] = kCout[l]; cc[l] = 2 * kCin[l]; bl[l] = kCout[l]; }
     cr[6] = emb_dims; cc[6] = 1024; bl[6] = emb_dims;
-    lr[0] = 512; lc[0] = 2 * emb_dims; lr[1] = 256; lc[1] = 512; lr[2] = 64; lc[2] = 256;
-    lr[3] = output_channels; lc[3] = 64;
-    bl[7] = 512; bl[8] = 256; bl[9] = 64;
+    for (int l = 0; l < 3; ++l) { lr[l] = bl[7 + l] = kHead[l]; lc[l] = l ? kHead[l - 1] : 2 * emb_dims; }
+    lr[3] = output_channels; lc[3] = kHead[2];
     for (int l = 0; l < 7; ++l) {
         PCD_CHECK_ARG(w->conv_w[l] != nullptr, "conv" + std::to_string(l + 1) + " weight is null");
         PCD_CHECK_ARG(w->conv_rows[l] == cr[l] && w->conv_cols[l] == cc[l],
@@ -522,7 +511,7 @@ int pcd_dgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes) {
     PCD_CHECK_ARG(m != nullptr, "model is null");
     PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
-    *bytes = layout(m, b).total;
+    *bytes = layout(m, b, nullptr).total;
     return PCD_OK;
 }
 
@@ -536,86 +525,56 @@ static int forward_impl(const pcd_dgcnn* m, const float* inputs, int64_t b, floa
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
     if (b == 0) return PCD_OK;
     PCD_CHECK_ARG(inputs != nullptr && out != nullptr, "inputs / out is null");
-    const Workspace w = layout(m, b);
+    const Workspace w = layout(m, b, workspace);
     PCD_CHECK_ARG(workspace != nullptr && workspace_bytes >= w.total,
                   "workspace of " + std::to_string(workspace_bytes) + " bytes is shorter than the " +
                       std::to_string(w.total) + " that pcd_dgcnn_workspace_bytes asks for");
     PCD_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
     PCD_CHECK_ARG(patch_base >= 0 && patch_base + b < kNoBadPatch, "patch_base + b must be in [0, 0x7f7f7f7f)");
     hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    float* cat = reinterpret_cast<float*>(ws + w.cat);
-    float* P = reinterpret_cast<float*>(ws + w.P);
-    int32_t* idx3 = reinterpret_cast<int32_t*>(ws + w.idx3);
-    int32_t* knn = reinterpret_cast<int32_t*>(ws + w.knn);
-    float* pooled = reinterpret_cast<float*>(ws + w.pooled);
-    float* h1 = reinterpret_cast<float*>(ws + w.h1);
-    float* h2 = reinterpret_cast<float*>(ws + w.h2);
-    float* h3 = reinterpret_cast<float*>(ws + w.h3);
-    int* flag = reinterpret_cast<int*>(ws + w.flag);
-    const int64_t cgs = 1024 * NODES;
 
     // the index columns first: a bad one ends the call before anything is computed from it (or, deferred, is
     // recorded in the caller's flag while the clamped index is used)
+    int rc;
     if (first_bad) {
-        hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, idx3,
-                           first_bad, (int)patch_base);
-        PCD_LAUNCH_CHECK();
+        if ((rc = index_lists(inputs, b, w.idx3, first_bad, (int)patch_base, st)) != PCD_OK) return rc;
     } else {
-        int bad = kNoBadPatch;
-        PCD_HIP(hipMemsetAsync(flag, 0x7f, sizeof(int), st));
-        hipLaunchKernelGGL(index_kernel, dim3((unsigned)cdiv(b * NODES * 3, 256)), dim3(256), 0, st, inputs, b, idx3, flag, 0);
-        PCD_LAUNCH_CHECK();
-        PCD_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        PCD_HIP(hipStreamSynchronize(st));
+        int bad;
+        if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
         PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
                                           " has an index column (rows 17:20) outside [0, 63] or NaN; no output written");
     }
 
-    int rc;
     for (int l = 0; l < 6; ++l) {
-        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
-        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
-        const int32_t* lists = idx3;
-        int kk = 3;
-        if (l >= 3) {
-            int32_t* mine = knn + (int64_t)(l - 3) * b * NODES * m->k;
-            if ((rc = run_knn(X, xgs, kCin[l], m->k, mine, b, st)) != PCD_OK) return rc;
-            lists = mine;
-            kk = m->k;
-        }
-        if ((rc = run_edge(m, l, X, xgs, lists, kk, P, cat + (int64_t)kCatOff[l] * NODES, cgs, b, st)) != PCD_OK) return rc;
+        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, m->k, b);
+        if (e.knn && (rc = dgcnn::knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
+        if ((rc = run_edge(m, l, e, w.P, w.cat + e.out_off, b, st)) != PCD_OK) return rc;
     }
     {   // conv7 + bn7 + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
-        GemmArgs a = conv_args(m->wt[6], m->emb, 1024, cat, cgs, nullptr, 0, b);
-        a.epi = EPI_POOL; a.s = m->s[6]; a.t = m->t[6]; a.poolT = pooled;
+        GemmArgs a = conv_args(m->wt[6], m->emb, 1024, w.cat, kCatStride, nullptr, 0, b);
+        a.epi = EPI_POOL; a.s = m->s[6]; a.t = m->t[6]; a.poolT = w.pooled;
         a.pool_dbg = debug ? debug->pooled : nullptr;
         if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
     }
-    const float* hin = pooled;
-    float* hout[3] = {h1, h2, h3};
-    int K = 2 * m->emb;
     for (int l = 0; l < 3; ++l) {
-        GemmArgs a = head_args(m->wt[7 + l], kHead[l], K, hin, hout[l], b);
+        GemmArgs a = head_args(m->wt[7 + l], kHead[l], l ? kHead[l - 1] : 2 * m->emb, l ? w.h[l - 1] : w.pooled, w.h[l], b);
         a.epi = EPI_AFFINE_LRELU; a.s = m->s[7 + l]; a.t = m->t[7 + l];
         if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
-        hin = hout[l];
-        K = kHead[l];
     }
     {   // linear4 (+ bias) -> out [b][out_ch]
-        GemmArgs a = head_args(m->wt[10], m->out_ch, 64, h3, out, b);
+        GemmArgs a = head_args(m->wt[10], m->out_ch, 64, w.h[2], out, b);
         a.G = 1; a.ygs = m->out_ch; a.yms = 1;          // Y(m, n) = out[n * out_ch + m]
         a.xgs = 1; a.xks = b;                           // X(k, n) = h3[k * b + n]
         a.epi = EPI_AFFINE; a.s = m->s[10]; a.t = m->t[10];
         if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
     }
     if (debug) {
-        if (debug->cat) PCD_HIP(hipMemcpyAsync(debug->cat, cat, b * cgs * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->cat) PCD_HIP(hipMemcpyAsync(debug->cat, w.cat, b * kCatStride * 4, hipMemcpyDeviceToDevice, st));
         if (debug->lists)
-            PCD_HIP(hipMemcpyAsync(debug->lists, knn, 3 * b * NODES * m->k * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h1) PCD_HIP(hipMemcpyAsync(debug->h1, h1, 512 * b * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h2) PCD_HIP(hipMemcpyAsync(debug->h2, h2, 256 * b * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h3) PCD_HIP(hipMemcpyAsync(debug->h3, h3, 64 * b * 4, hipMemcpyDeviceToDevice, st));
+            PCD_HIP(hipMemcpyAsync(debug->lists, w.knn, 3 * b * NODES * m->k * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h1) PCD_HIP(hipMemcpyAsync(debug->h1, w.h[0], 512 * b * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h2) PCD_HIP(hipMemcpyAsync(debug->h2, w.h[1], 256 * b * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->h3) PCD_HIP(hipMemcpyAsync(debug->h3, w.h[2], 64 * b * 4, hipMemcpyDeviceToDevice, st));
     }
     return PCD_OK;
 }
@@ -638,7 +597,7 @@ int pcd_dgcnn_knn(const float* x, int64_t b, int channels, int k, int32_t* lists
     PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
     if (b == 0) return PCD_OK;
     PCD_CHECK_ARG(x != nullptr && lists != nullptr, "x / lists is null");
-    return run_knn(x, (int64_t)channels * NODES, channels, k, lists, b, as_stream(stream));
+    return dgcnn::knn(x, (int64_t)channels * NODES, channels, k, lists, b, as_stream(stream));
 }
 
 int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b, const int32_t* lists, int list_len,
@@ -654,7 +613,7 @@ int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b,
     StreamTemps tmp(st);
     float* P;
     PCD_HIP(tmp.alloc(&P, b * 2 * kCout[l] * NODES * sizeof(float)));
-    const int rc = run_edge(m, l, x, (int64_t)kCin[l] * NODES, lists, list_len, P, out, (int64_t)kCout[l] * NODES, b, st);
+    const int rc = run_edge(m, l, edge_layer_alone(l, x, lists, list_len), P, out, b, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
@@ -675,8 +634,8 @@ int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64
     float *Wt, *poolT = nullptr;
     const int64_t wn = (int64_t)m_rows * k_cols;
     PCD_HIP(tmp.alloc(&Wt, wn * sizeof(float)));
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)cdiv(wn, 256)), dim3(256), 0, st, w, m_rows, k_cols, Wt);
-    PCD_LAUNCH_CHECK();
+    int rc = dgcnn::transpose(w, m_rows, k_cols, Wt, st);
+    if (rc != PCD_OK) return rc;
     GemmArgs a = nodes == NODES
                      ? conv_args(Wt, m_rows, k_cols, x, (int64_t)k_cols * NODES, y, (int64_t)m_rows * NODES, b)
                      : head_args(Wt, m_rows, k_cols, x, y, b);
@@ -685,8 +644,7 @@ int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64
         PCD_HIP(tmp.alloc(&poolT, 2 * (int64_t)m_rows * b * sizeof(float)));
         a.poolT = poolT; a.pool_dbg = y; a.Y = nullptr;
     }
-    const int rc = launch_gemm(a, st);
-    if (rc != PCD_OK) return rc;
+    if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
 }

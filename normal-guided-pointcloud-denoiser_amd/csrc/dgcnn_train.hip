@@ -21,6 +21,9 @@
 // (dgcnn.hip: float32 chains of 8 k joined in double, rounded once -- the batch norms of a small batch multiply the
 // forward's rounding by up to 1 / sqrt(eps)); the data gradients W^T dY on the forward's own gemm_kernel<0> with the
 // add-into-Y epilogue.  -ffp-contract=off stays: fmaf where a fused multiply-add is meant.
+// On the host an edge layer is three named views: where it reads and writes (EdgeLayer, pcd_dgcnn.h: the inference
+// pass's wiring), what it keeps from forward to backward (EdgeState) and the scratch all layers share (EdgeScratch);
+// the whole step carves them from the caller's workspace, the single-layer stage entries from a temporary allocation.
 #include <math.h>
 
 #include <algorithm>
@@ -29,20 +32,12 @@
 #include "pcd_host.h"
 
 using namespace pcd;
+using namespace pcd::dgcnn;
 
 namespace {
 
-constexpr int NODES = 64;
 constexpr int CHUNK = 8;             // patches per partial of the batch statistics
-const int kCin[6] = {17, 64, 64, 128, 256, 256};
-const int kCout[6] = {64, 64, 128, 256, 256, 256};
-const int kCatOff[6] = {0, 64, 128, 256, 512, 768};
-constexpr int64_t kMaxBatch = 1 << 20;
-constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
 // An edge value y = A[j] + B[i] and its normalised z = s y + t are formed in double from the stored float32 products
 // and the double statistics (s = gamma / sigma, t = beta - s mu), and rounded once where they are stored: the forward,
 // the statistics and the backward all see the same y and the same sign of z.
@@ -53,6 +48,15 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);   // a fixed tree; every lane ends with the same bits
     return v;
+}
+// part [chunk][C][2]: the wave's two sums (lane = threadIdx.x & 63) are chunk blockIdx.x's partial of channel c
+__device__ __forceinline__ void put_partial(double* part, int C, int c, double s, double q) {
+    s = wave_sum(s);
+    q = wave_sum(q);
+    if ((threadIdx.x & 63) == 0) {
+        part[((int64_t)blockIdx.x * C + c) * 2] = s;
+        part[((int64_t)blockIdx.x * C + c) * 2 + 1] = q;
+    }
 }
 
 // W [Cout][2 Cin] -> Wt [Cin][2 Cout] and Ws [2 Cout][Cin] of [W_a ; W_b - W_a]
@@ -85,12 +89,7 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float* P, int Cou
             q = fma(y, y, q);
         }
     }
-    s = wave_sum(s);
-    q = wave_sum(q);
-    if (i == 0) {
-        part[((int64_t)blockIdx.x * Cout + c) * 2] = s;
-        part[((int64_t)blockIdx.x * Cout + c) * 2 + 1] = q;
-    }
+    put_partial(part, Cout, c, s, q);
 }
 
 // the same over Y [b][C][64]
@@ -104,15 +103,10 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* Y, int C, i
         s += y;
         q = fma(y, y, q);
     }
-    s = wave_sum(s);
-    q = wave_sum(q);
-    if (i == 0) {
-        part[((int64_t)blockIdx.x * C + c) * 2] = s;
-        part[((int64_t)blockIdx.x * C + c) * 2 + 1] = q;
-    }
+    put_partial(part, C, c, s, q);
 }
 
-struct BnArgs {
+struct BnArgs {               // one batch norm (bn_params) and, from run_finalize, its statistics' partials and results
     const double* part;
     int nchunks, C;
     double N, eps, momentum;
@@ -227,12 +221,7 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* P, in
         sb += (double)dz;
         sg = fma((double)dz, (y - mu) * istd, sg);
     }
-    sb = wave_sum(sb);
-    sg = wave_sum(sg);
-    if (i == 0) {
-        part[((int64_t)blockIdx.x * Cout + c) * 2] = sb;
-        part[((int64_t)blockIdx.x * Cout + c) * 2 + 1] = sg;
-    }
+    put_partial(part, Cout, c, sb, sg);
 }
 
 // conv7: dz[p][c][i] = (gmax [i = arg7] + gmean / 64) lrelu'(s y + t); dpooled [b][2 C]
@@ -256,12 +245,7 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float* Y, in
         sb += (double)dz;
         sg = fma((double)dz, ((double)y - mu) * istd, sg);
     }
-    sb = wave_sum(sb);
-    sg = wave_sum(sg);
-    if (i == 0) {
-        part[((int64_t)blockIdx.x * C + c) * 2] = sb;
-        part[((int64_t)blockIdx.x * C + c) * 2 + 1] = sg;
-    }
+    put_partial(part, C, c, sb, sg);
 }
 
 // partials in chunk order -> dstat [2][C] (d beta, d gamma, double) and the float gradients
@@ -426,14 +410,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
             }
         }
     }
-    // C layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int k = k0 + wn + acol;
     float* out = a.part + (int64_t)blockIdx.x * a.M * a.K;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * arow;
+            const int m = mfma_row(m0 + wm + 32 * h, r, arow);
             if (m < a.M && k < a.K) out[(int64_t)m * a.K + k] = acc[h][r];
         }
     }
@@ -471,76 +454,93 @@ int64_t wgrad_pps(int64_t b) {
 }
 int64_t wgrad_splits(int64_t b) { return std::max<int64_t>(1, cdiv(b, wgrad_pps(b))); }
 
-int run_wgrad(const float* dY, int64_t ygs, int M, const float* X, int64_t xgs, int K, int64_t b, float* part, float* out,
-              int mode, hipStream_t st) {
-    WgradArgs a{};
-    a.dY = dY; a.X = X; a.part = part; a.ygs = ygs; a.xgs = xgs; a.b = b; a.pps = wgrad_pps(b); a.M = M; a.K = K;
+// a: dY, ygs, M, X, xgs, K and part are the caller's; out [M][K] (mode 0) or [M / 2][2 K] (mode 1)
+int run_wgrad(WgradArgs a, int64_t b, float* out, int mode, hipStream_t st) {
+    a.b = b;
+    a.pps = wgrad_pps(b);
     const int splits = (int)wgrad_splits(b);
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)splits, (unsigned)cdiv(M, WM), (unsigned)cdiv(K, WK)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)splits, (unsigned)cdiv(a.M, WM), (unsigned)cdiv(a.K, WK)), dim3(256), 0,
+                       st, a);
     PCD_LAUNCH_CHECK();
-    const int64_t n = mode == 0 ? (int64_t)M * K : (int64_t)(M / 2) * K;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, part, splits, M, K, out, mode);
+    const int64_t n = mode == 0 ? (int64_t)a.M * a.K : (int64_t)(a.M / 2) * a.K;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, a.part, splits, a.M, a.K, out,
+                       mode);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
 
-struct Bn {                  // one batch norm's parameters and buffers (device)
-    const float *gamma, *beta;
-    float *rmean, *rvar;
-    int64_t* tracked;
-    double eps, momentum;
-};
-
-int run_finalize(const Bn& bn, const double* part, int64_t b, int C, double N, double* stat, double* sti, hipStream_t st) {
+BnArgs bn_params(const float* gamma, const float* beta, float* rmean, float* rvar, int64_t* tracked, double eps,
+                 double momentum) {
     BnArgs a{};
-    a.part = part; a.nchunks = (int)cdiv(b, CHUNK); a.C = C; a.N = N; a.eps = bn.eps; a.momentum = bn.momentum;
-    a.gamma = bn.gamma; a.beta = bn.beta; a.rmean = bn.rmean; a.rvar = bn.rvar; a.tracked = bn.tracked;
-    a.stat = stat; a.sti = sti;
+    a.gamma = gamma; a.beta = beta; a.rmean = rmean; a.rvar = rvar; a.tracked = tracked; a.eps = eps; a.momentum = momentum;
+    return a;
+}
+
+int run_finalize(BnArgs a, const double* part, int64_t b, int C, double N, double* stat, double* sti, hipStream_t st) {
+    a.part = part; a.nchunks = (int)cdiv(b, CHUNK); a.C = C; a.N = N; a.stat = stat; a.sti = sti;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)cdiv(C, 64)), dim3(64), 0, st, a);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
 
-// edge layer l forward: X -> P = [A ; B], statistics, out and the arg-max bytes
-int edge_forward(int l, const float* Wt, const Bn& bn, const float* X, int64_t xgs, const int32_t* lists, int kk, float* P,
-                 double* part, double* stat, double* sti, float* out, int64_t ogs, uint8_t* arg, int64_t ags, int64_t b,
+struct EdgeState {           // what an edge layer keeps between its forward and its backward
+    float *Wt, *Ws;          // the split weight [W_a ; W_b - W_a]: [Cin][2 Cout] (forward), [2 Cout][Cin] (data gradient)
+    float* P;                // [b][2 Cout][64]: A rows, then B rows
+    uint8_t* arg;            // [b][Cout][64], patch stride ags: the arg-max slot of every output
+    int64_t ags;
+    double *stat, *sti;      // [3][Cout]: mu, biased var, 1 / sqrt(var + eps); [2][Cout]: s, t
+};
+struct EdgeScratch {         // shared by all layers
+    double *part, *dstat;    // [chunks][C][2]; [2][C]: d beta, d gamma
+    float *dP, *wpart;       // [b][2 Cout][64]; [splits][2 Cout][Cin]
+    int32_t *rev_off, *rev;  // the reversed lists of the layer at hand
+};
+struct EdgeGrads {           // g = dL/d out laid out as out is; dX (null: not wanted) as X is, added into or stored
+    const float* g;
+    float *dgamma, *dbeta, *dW, *dX;
+    bool add;
+};
+
+// edge layer forward: X -> P = [A ; B], statistics, out (patch stride e.ogs) and the arg-max bytes
+int edge_forward(const EdgeLayer& e, const EdgeState& s, const EdgeScratch& scr, const BnArgs& bn, float* out, int64_t b,
                  hipStream_t st) {
-    const int Cin = kCin[l], Cout = kCout[l];
-    int rc = dgcnn::conv_gemm(Wt, 2 * Cout, Cin, X, xgs, P, (int64_t)2 * Cout * NODES, b, dgcnn::EPI_PLAIN, true, st);
+    const int Cout = e.Cout;
+    int rc = conv_gemm(s.Wt, 2 * Cout, e.Cin, e.X, e.xgs, s.P, (int64_t)2 * Cout * NODES, b, EPI_PLAIN, true, st);
     if (rc != PCD_OK) return rc;
     const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(Cout, 4));
-    hipLaunchKernelGGL(edge_stats_kernel, chunks, dim3(256), 0, st, P, Cout, lists, kk, b, part);
+    hipLaunchKernelGGL(edge_stats_kernel, chunks, dim3(256), 0, st, s.P, Cout, e.lists, e.kk, b, scr.part);
     PCD_LAUNCH_CHECK();
-    if ((rc = run_finalize(bn, part, b, Cout, (double)b * NODES * kk, stat, sti, st)) != PCD_OK) return rc;
-    hipLaunchKernelGGL(edge_train_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
-                       sti, out, ogs, arg, ags);
+    if ((rc = run_finalize(bn, scr.part, b, Cout, (double)b * NODES * e.kk, s.stat, s.sti, st)) != PCD_OK) return rc;
+    hipLaunchKernelGGL(edge_train_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, s.P, Cout, e.lists,
+                       e.kk, s.sti, out, e.ogs, s.arg, s.ags);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
 
-// edge layer l backward: g = dL/d out -> d gamma, d beta, dP = [dA ; dB], dW (module layout), dX (null: not wanted)
-int edge_backward(int l, const float* Ws, const float* X, int64_t xgs, const int32_t* lists, int kk, const int32_t* rev_off,
-                  const int32_t* rev, const float* P, const uint8_t* arg, int64_t ags, const float* g, int64_t ggs,
-                  const double* stat, const double* sti, double* part, double* dstat, float* dP, float* wpart,
-                  float* dgamma, float* dbeta, float* dW, float* dX, int64_t dxgs, bool add, int64_t b, hipStream_t st) {
-    const int Cin = kCin[l], Cout = kCout[l];
+// edge layer backward: gr.g -> d gamma, d beta, scr.dP = [dA ; dB], dW (module layout), dX
+int edge_backward(const EdgeLayer& e, const EdgeState& s, const EdgeScratch& scr, const EdgeGrads& gr, int64_t b,
+                  hipStream_t st) {
+    const int Cin = e.Cin, Cout = e.Cout;
     const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(Cout, 4));
-    hipLaunchKernelGGL(edge_bwd_reduce_kernel, chunks, dim3(256), 0, st, P, Cout, lists, kk, arg, ags, g, ggs, stat, sti, b, part);
+    hipLaunchKernelGGL(edge_bwd_reduce_kernel, chunks, dim3(256), 0, st, s.P, Cout, e.lists, e.kk, s.arg, s.ags, gr.g, e.ogs,
+                       s.stat, s.sti, b, scr.part);
     PCD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(Cout, 64)), dim3(64), 0, st, part, (int)cdiv(b, CHUNK), Cout,
-                       dstat, dgamma, dbeta);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(Cout, 64)), dim3(64), 0, st, scr.part,
+                       (int)cdiv(b, CHUNK), Cout, scr.dstat, gr.dgamma, gr.dbeta);
     PCD_LAUNCH_CHECK();
-    const double invN = 1.0 / ((double)b * NODES * kk);
-    hipLaunchKernelGGL(edge_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, P, Cout, lists, kk,
-                       rev_off, rev, arg, ags, g, ggs, stat, sti, dstat, invN, dP);
+    const double invN = 1.0 / ((double)b * NODES * e.kk);
+    hipLaunchKernelGGL(edge_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(Cout, 4)), dim3(256), 0, st, s.P, Cout, e.lists,
+                       e.kk, scr.rev_off, scr.rev, s.arg, s.ags, gr.g, e.ogs, s.stat, s.sti, scr.dstat, invN, scr.dP);
     PCD_LAUNCH_CHECK();
-    int rc;
-    if (dX) {   // dX (+)= [W_a ; W_b - W_a]^T dP: the split weight [2 Cout][Cin] is the GEMM's transposed operand
-        rc = dgcnn::conv_gemm(Ws, Cin, 2 * Cout, dP, (int64_t)2 * Cout * NODES, dX, dxgs, b,
-                              add ? dgcnn::EPI_ADD : dgcnn::EPI_PLAIN, false, st);
+    if (gr.dX) {   // dX (+)= [W_a ; W_b - W_a]^T dP: the split weight [2 Cout][Cin] is the GEMM's transposed operand
+        const int rc = conv_gemm(s.Ws, Cin, 2 * Cout, scr.dP, (int64_t)2 * Cout * NODES, gr.dX, e.xgs, b,
+                                 gr.add ? EPI_ADD : EPI_PLAIN, false, st);
         if (rc != PCD_OK) return rc;
     }
-    return run_wgrad(dP, (int64_t)2 * Cout * NODES, 2 * Cout, X, xgs, Cin, b, wpart, dW, 1, st);
+    WgradArgs a{};
+    a.dY = scr.dP; a.ygs = (int64_t)2 * Cout * NODES; a.M = 2 * Cout;
+    a.X = e.X; a.xgs = e.xgs; a.K = Cin; a.part = scr.wpart;
+    return run_wgrad(a, b, gr.dW, 1, st);
 }
 
 int run_reverse(const int32_t* lists, int kk, int32_t* rev_off, int32_t* rev, int64_t b, hipStream_t st) {
@@ -556,41 +556,58 @@ int run_pack(const float* W, int l, float* Wt, float* Ws, hipStream_t st) {
     return PCD_OK;
 }
 
-struct TrainWs {             // byte offsets into the workspace
-    int64_t wt[6], ws[6], w7t, cat, P[6], arg, idx3, knn, rev_off, rev, Y7, arg7, dcat, dP, stat[7], sti[7], dstat, part,
-        wpart, flag, total;
+// The whole step (TrainWs) and the single-layer stage entries (StageWs) carve their per-layer state and the shared
+// scratch with the same two functions.
+EdgeState carve_edge(Carver& c, int l, int64_t b) {
+    const int Cin = kCin[l], Cout = kCout[l];
+    EdgeState s{};
+    s.Wt = c.carve<float>((int64_t)2 * Cin * Cout * 4);
+    s.Ws = c.carve<float>((int64_t)2 * Cin * Cout * 4);
+    s.P = c.carve<float>(b * 2 * Cout * NODES * 4);
+    s.arg = c.carve<uint8_t>(b * Cout * NODES);
+    s.ags = (int64_t)Cout * NODES;
+    s.stat = c.carve<double>((int64_t)3 * Cout * 8);
+    s.sti = c.carve<double>((int64_t)2 * Cout * 8);
+    return s;
+}
+// C channels at most, P_rows rows of dP, lists of kk at most, wfloats floats per partial of the weight gradient
+EdgeScratch carve_scratch(Carver& c, int64_t b, int C, int P_rows, int kk, int64_t wfloats) {
+    EdgeScratch s{};
+    s.part = c.carve<double>(cdiv(b, CHUNK) * C * 2 * 8);
+    s.dstat = c.carve<double>((int64_t)2 * C * 8);
+    s.dP = c.carve<float>(b * P_rows * NODES * 4);
+    s.wpart = c.carve<float>(wgrad_splits(b) * wfloats * 4);
+    s.rev_off = c.carve<int32_t>(b * (NODES + 1) * 4);
+    s.rev = c.carve<int32_t>(b * NODES * kk * 4);
+    return s;
+}
+
+struct TrainWs {
+    EdgeState edge[6];
+    EdgeScratch scr;
+    float *w7t, *cat, *dcat; // conv7's weight transposed [1024][emb]; the concatenation [b][1024][64] and its gradient
+    float* Y7;               // [b][emb][64]: conv7's product, then its gradient
+    uint8_t* arg7;           // [b][emb]
+    double *stat7, *sti7;    // as an edge layer's
+    int32_t *idx3, *knn, *flag;   // [b][64][3], [3][b][64][k], [1]
+    int64_t total;           // bytes
 };
-TrainWs tlayout(int k, int emb, int64_t b) {
+TrainWs tlayout(int k, int emb, int64_t b, void* ws) {
     TrainWs w{};
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    for (int l = 0; l < 6; ++l) {
-        w.wt[l] = take((int64_t)2 * kCin[l] * kCout[l] * 4);
-        w.ws[l] = take((int64_t)2 * kCin[l] * kCout[l] * 4);
-    }
-    w.w7t = take((int64_t)1024 * emb * 4);
-    w.cat = take(b * 1024 * NODES * 4);
-    for (int l = 0; l < 6; ++l) w.P[l] = take(b * 2 * kCout[l] * NODES * 4);
-    w.arg = take(b * 1024 * NODES);
-    w.idx3 = take(b * NODES * 3 * 4);
-    w.knn = take(3 * b * NODES * k * 4);
-    w.rev_off = take(b * (NODES + 1) * 4);
-    w.rev = take(b * NODES * std::max(3, k) * 4);
-    w.Y7 = take(b * emb * NODES * 4);
-    w.arg7 = take(b * emb);
-    w.dcat = take(b * 1024 * NODES * 4);
-    w.dP = take(b * 512 * NODES * 4);
-    const int maxC = std::max(256, emb);
-    for (int l = 0; l < 7; ++l) {
-        const int C = l < 6 ? kCout[l] : emb;
-        w.stat[l] = take((int64_t)3 * C * 8);
-        w.sti[l] = take((int64_t)2 * C * 8);
-    }
-    w.dstat = take((int64_t)2 * maxC * 8);
-    w.part = take(cdiv(b, CHUNK) * maxC * 2 * 8);
-    w.wpart = take(wgrad_splits(b) * std::max<int64_t>((int64_t)emb * 1024, 512 * 256) * 4);
-    w.flag = take(4);
-    w.total = o;
+    Carver c{ws};
+    for (int l = 0; l < 6; ++l) w.edge[l] = carve_edge(c, l, b);
+    w.w7t = c.carve<float>((int64_t)1024 * emb * 4);
+    w.cat = c.carve<float>(b * 1024 * NODES * 4);
+    w.dcat = c.carve<float>(b * 1024 * NODES * 4);
+    w.idx3 = c.carve<int32_t>(b * NODES * 3 * 4);
+    w.knn = c.carve<int32_t>(3 * b * NODES * k * 4);
+    w.Y7 = c.carve<float>(b * emb * NODES * 4);
+    w.arg7 = c.carve<uint8_t>(b * emb);
+    w.stat7 = c.carve<double>((int64_t)3 * emb * 8);
+    w.sti7 = c.carve<double>((int64_t)2 * emb * 8);
+    w.scr = carve_scratch(c, b, std::max(256, emb), 512, std::max(3, k), std::max<int64_t>((int64_t)emb * 1024, 512 * 256));
+    w.flag = c.carve<int32_t>(4);
+    w.total = c.used;
     return w;
 }
 
@@ -609,9 +626,6 @@ int check_ws(const TrainWs& w, const void* workspace, int64_t bytes) {
     return PCD_OK;
 }
 
-template <class T>
-T* at(void* ws, int64_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
-
 }  // namespace
 
 extern "C" {
@@ -620,7 +634,7 @@ int pcd_dgcnn_train_workspace_bytes(int k, int emb_dims, int64_t b, int64_t* byt
     PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
     const int rc = check_dims(k, emb_dims, b);
     if (rc != PCD_OK) return rc;
-    *bytes = tlayout(k, emb_dims, b).total;
+    *bytes = tlayout(k, emb_dims, b, nullptr).total;
     return PCD_OK;
 }
 
@@ -640,67 +654,41 @@ int pcd_dgcnn_train_forward(const pcd_dgcnn_train_params* prm, int k, int emb_di
         PCD_CHECK_ARG(prm->bn_eps[l] >= 0.0, "bn" + name + " eps is invalid");
         PCD_CHECK_ARG(prm->bn_momentum[l] >= 0.0 && prm->bn_momentum[l] <= 1.0, "bn" + name + " momentum must be in [0, 1]");
     }
-    const TrainWs w = tlayout(k, emb_dims, b);
+    const TrainWs w = tlayout(k, emb_dims, b, workspace);
     if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
     hipStream_t st = as_stream(stream);
-    const int64_t cgs = 1024 * NODES;
-    float* cat = at<float>(workspace, w.cat);
-    int32_t* idx3 = at<int32_t>(workspace, w.idx3);
-    int32_t* knn = at<int32_t>(workspace, w.knn);
-    double* part = at<double>(workspace, w.part);
-    uint8_t* arg = at<uint8_t>(workspace, w.arg);
-    int* flag = at<int>(workspace, w.flag);
 
-    {   // the index columns first: a bad one ends the call before anything is computed or a buffer updated
-        int bad = kNoBadPatch;
-        PCD_HIP(hipMemsetAsync(flag, 0x7f, sizeof(int), st));
-        if ((rc = dgcnn::index_lists(inputs, b, idx3, flag, st)) != PCD_OK) return rc;
-        PCD_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        PCD_HIP(hipStreamSynchronize(st));
-        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
-                                          " has an index column (rows 17:20) outside [0, 63] or NaN; nothing written");
-    }
+    // the index columns first: a bad one ends the call before anything is computed or a buffer updated
+    int bad;
+    if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
+    PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
+                                      " has an index column (rows 17:20) outside [0, 63] or NaN; nothing written");
     for (int l = 0; l < 6; ++l)
-        if ((rc = run_pack(prm->conv_w[l], l, at<float>(workspace, w.wt[l]), at<float>(workspace, w.ws[l]), st)) != PCD_OK)
-            return rc;
-    if ((rc = dgcnn::transpose(prm->conv_w[6], emb_dims, 1024, at<float>(workspace, w.w7t), st)) != PCD_OK) return rc;
+        if ((rc = run_pack(prm->conv_w[l], l, w.edge[l].Wt, w.edge[l].Ws, st)) != PCD_OK) return rc;
+    if ((rc = transpose(prm->conv_w[6], emb_dims, 1024, w.w7t, st)) != PCD_OK) return rc;
 
     auto bn_of = [&](int l) {
-        return Bn{prm->bn_weight[l], prm->bn_bias[l], prm->bn_mean[l], prm->bn_var[l], prm->bn_tracked[l], prm->bn_eps[l],
-                  prm->bn_momentum[l]};
+        return bn_params(prm->bn_weight[l], prm->bn_bias[l], prm->bn_mean[l], prm->bn_var[l], prm->bn_tracked[l],
+                         prm->bn_eps[l], prm->bn_momentum[l]);
     };
     for (int l = 0; l < 6; ++l) {
-        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
-        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
-        const int32_t* lists = idx3;
-        int kk = 3;
-        if (l >= 3) {
-            int32_t* mine = knn + (int64_t)(l - 3) * b * NODES * k;
-            if ((rc = dgcnn::knn(X, xgs, kCin[l], k, mine, b, st)) != PCD_OK) return rc;
-            lists = mine;
-            kk = k;
-        }
-        rc = edge_forward(l, at<float>(workspace, w.wt[l]), bn_of(l), X, xgs, lists, kk, at<float>(workspace, w.P[l]), part,
-                          at<double>(workspace, w.stat[l]), at<double>(workspace, w.sti[l]),
-                          cat + (int64_t)kCatOff[l] * NODES, cgs, arg + (int64_t)kCatOff[l] * NODES, cgs, b, st);
-        if (rc != PCD_OK) return rc;
+        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, k, b);
+        if (e.knn && (rc = knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
+        if ((rc = edge_forward(e, w.edge[l], w.scr, bn_of(l), w.cat + e.out_off, b, st)) != PCD_OK) return rc;
     }
     {   // conv7: the product is stored (the backward turns it into dY in place), then statistics and pooling
-        float* Y7 = at<float>(workspace, w.Y7);
-        rc = dgcnn::conv_gemm(at<float>(workspace, w.w7t), emb_dims, 1024, cat, cgs, Y7, (int64_t)emb_dims * NODES, b,
-                              dgcnn::EPI_PLAIN, true, st);
+        rc = conv_gemm(w.w7t, emb_dims, 1024, w.cat, kCatStride, w.Y7, (int64_t)emb_dims * NODES, b, EPI_PLAIN, true, st);
         if (rc != PCD_OK) return rc;
         const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
-        hipLaunchKernelGGL(row_stats_kernel, chunks, dim3(256), 0, st, Y7, emb_dims, b, part);
+        hipLaunchKernelGGL(row_stats_kernel, chunks, dim3(256), 0, st, w.Y7, emb_dims, b, w.scr.part);
         PCD_LAUNCH_CHECK();
-        rc = run_finalize(bn_of(6), part, b, emb_dims, (double)b * NODES, at<double>(workspace, w.stat[6]),
-                          at<double>(workspace, w.sti[6]), st);
+        rc = run_finalize(bn_of(6), w.scr.part, b, emb_dims, (double)b * NODES, w.stat7, w.sti7, st);
         if (rc != PCD_OK) return rc;
-        hipLaunchKernelGGL(pool_train_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, Y7, emb_dims,
-                           at<double>(workspace, w.sti[6]), pooled, at<uint8_t>(workspace, w.arg7));
+        hipLaunchKernelGGL(pool_train_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, w.Y7,
+                           emb_dims, w.sti7, pooled, w.arg7);
         PCD_LAUNCH_CHECK();
     }
-    if (lists_out) PCD_HIP(hipMemcpyAsync(lists_out, knn, 3 * b * NODES * k * 4, hipMemcpyDeviceToDevice, st));
+    if (lists_out) PCD_HIP(hipMemcpyAsync(lists_out, w.knn, 3 * b * NODES * k * 4, hipMemcpyDeviceToDevice, st));
     return PCD_OK;
 }
 
@@ -715,54 +703,42 @@ int pcd_dgcnn_train_backward(int k, int emb_dims, const float* inputs, int64_t b
     for (int l = 0; l < 7; ++l)
         PCD_CHECK_ARG(grads->conv_w[l] && grads->bn_weight[l] && grads->bn_bias[l],
                       "gradient " + std::to_string(l + 1) + " has a null pointer");
-    const TrainWs w = tlayout(k, emb_dims, b);
+    const TrainWs w = tlayout(k, emb_dims, b, workspace);
     if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
     hipStream_t st = as_stream(stream);
-    const int64_t cgs = 1024 * NODES;
-    float* cat = at<float>(workspace, w.cat);
-    float* dcat = at<float>(workspace, w.dcat);
-    float* dP = at<float>(workspace, w.dP);
-    float* wpart = at<float>(workspace, w.wpart);
-    double* part = at<double>(workspace, w.part);
-    double* dstat = at<double>(workspace, w.dstat);
-    int32_t* idx3 = at<int32_t>(workspace, w.idx3);
-    int32_t* knn = at<int32_t>(workspace, w.knn);
-    int32_t* rev_off = at<int32_t>(workspace, w.rev_off);
-    int32_t* rev = at<int32_t>(workspace, w.rev);
-    const uint8_t* arg = at<uint8_t>(workspace, w.arg);
+    const EdgeScratch& scr = w.scr;
     {   // conv7: pooling, LeakyReLU and batch norm, dY in place of the stored product
-        float* Y7 = at<float>(workspace, w.Y7);
-        const uint8_t* arg7 = at<uint8_t>(workspace, w.arg7);
-        const double* stat = at<double>(workspace, w.stat[6]);
-        const double* sti = at<double>(workspace, w.sti[6]);
         const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
-        hipLaunchKernelGGL(pool_bwd_reduce_kernel, chunks, dim3(256), 0, st, Y7, emb_dims, arg7, d_pooled, stat, sti, b, part);
+        hipLaunchKernelGGL(pool_bwd_reduce_kernel, chunks, dim3(256), 0, st, w.Y7, emb_dims, w.arg7, d_pooled, w.stat7,
+                           w.sti7, b, scr.part);
         PCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(emb_dims, 64)), dim3(64), 0, st, part,
-                           (int)cdiv(b, CHUNK), emb_dims, dstat, grads->bn_weight[6], grads->bn_bias[6]);
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(emb_dims, 64)), dim3(64), 0, st, scr.part,
+                           (int)cdiv(b, CHUNK), emb_dims, scr.dstat, grads->bn_weight[6], grads->bn_bias[6]);
         PCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pool_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, Y7,
-                           emb_dims, arg7, d_pooled, stat, sti, dstat, 1.0 / ((double)b * NODES));
+        hipLaunchKernelGGL(pool_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, w.Y7,
+                           emb_dims, w.arg7, d_pooled, w.stat7, w.sti7, scr.dstat, 1.0 / ((double)b * NODES));
         PCD_LAUNCH_CHECK();
         // dcat = W7^T dY: W7 [emb][1024] itself is the GEMM's transposed operand; every slice's first contribution
-        rc = dgcnn::conv_gemm(conv7_w, 1024, emb_dims, Y7, (int64_t)emb_dims * NODES, dcat, cgs, b, dgcnn::EPI_PLAIN, false, st);
+        rc = conv_gemm(conv7_w, 1024, emb_dims, w.Y7, (int64_t)emb_dims * NODES, w.dcat, kCatStride, b, EPI_PLAIN, false, st);
         if (rc != PCD_OK) return rc;
-        rc = run_wgrad(Y7, (int64_t)emb_dims * NODES, emb_dims, cat, cgs, 1024, b, wpart, grads->conv_w[6], 0, st);
-        if (rc != PCD_OK) return rc;
+        WgradArgs a{};
+        a.dY = w.Y7; a.ygs = (int64_t)emb_dims * NODES; a.M = emb_dims;
+        a.X = w.cat; a.xgs = kCatStride; a.K = 1024; a.part = scr.wpart;
+        if ((rc = run_wgrad(a, b, grads->conv_w[6], 0, st)) != PCD_OK) return rc;
     }
+    const int32_t* reversed = nullptr;   // the lists scr.rev holds: layers 1-3 share theirs
     for (int l = 5; l >= 0; --l) {
-        const float* X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
-        const int64_t xgs = l == 0 ? 20 * NODES : cgs;
-        const int32_t* lists = l >= 3 ? knn + (int64_t)(l - 3) * b * NODES * k : idx3;
-        const int kk = l >= 3 ? k : 3;
-        if (l >= 2 && (rc = run_reverse(lists, kk, rev_off, rev, b, st)) != PCD_OK) return rc;   // layers 1-3 share theirs
-        // the layer's input slice already holds conv7's contribution: this layer's is added second
-        float* dX = l == 0 ? nullptr : dcat + (int64_t)kCatOff[l - 1] * NODES;
-        rc = edge_backward(l, at<float>(workspace, w.ws[l]), X, xgs, lists, kk, rev_off, rev, at<float>(workspace, w.P[l]),
-                           arg + (int64_t)kCatOff[l] * NODES, cgs, dcat + (int64_t)kCatOff[l] * NODES, cgs,
-                           at<double>(workspace, w.stat[l]), at<double>(workspace, w.sti[l]), part, dstat, dP, wpart,
-                           grads->bn_weight[l], grads->bn_bias[l], grads->conv_w[l], dX, cgs, true, b, st);
-        if (rc != PCD_OK) return rc;
+        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, k, b);
+        if (e.lists != reversed) {
+            if ((rc = run_reverse(e.lists, e.kk, scr.rev_off, scr.rev, b, st)) != PCD_OK) return rc;
+            reversed = e.lists;
+        }
+        // the gradient of a slice of cat is that slice of dcat, which already holds conv7's contribution: this
+        // layer's is added second.  The network's inputs take none.
+        EdgeGrads gr{};
+        gr.g = w.dcat + e.out_off; gr.dX = e.X == inputs ? nullptr : w.dcat + (e.X - w.cat); gr.add = true;
+        gr.dgamma = grads->bn_weight[l]; gr.dbeta = grads->bn_bias[l]; gr.dW = grads->conv_w[l];
+        if ((rc = edge_backward(e, w.edge[l], scr, gr, b, st)) != PCD_OK) return rc;
     }
     return PCD_OK;
 }
@@ -781,37 +757,29 @@ int pcd_dgcnn_wgrad(const float* dy, const float* x, int m_rows, int k_cols, int
     PCD_CHECK_ARG(dy != nullptr && x != nullptr && dw != nullptr, "dy / x / dw is null");
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
-    float* part;
-    PCD_HIP(tmp.alloc(&part, wgrad_splits(b) * (int64_t)m_rows * k_cols * sizeof(float)));
-    const int rc = run_wgrad(dy, (int64_t)m_rows * NODES, m_rows, x, (int64_t)k_cols * NODES, k_cols, b, part, dw, 0, st);
+    WgradArgs a{};
+    a.dY = dy; a.ygs = (int64_t)m_rows * NODES; a.M = m_rows;
+    a.X = x; a.xgs = (int64_t)k_cols * NODES; a.K = k_cols;
+    PCD_HIP(tmp.alloc(&a.part, wgrad_splits(b) * (int64_t)m_rows * k_cols * sizeof(float)));
+    const int rc = run_wgrad(a, b, dw, 0, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
 }
 
-// the edge stage's scratch: one allocation, carved
+// the edge stage's scratch: one allocation, carved as the whole step's workspace is
 namespace {
 struct StageWs {
-    int64_t wt, ws, P, part, sti, stat, dstat, rev_off, rev, dP, wpart, arg, total;
+    EdgeState edge;
+    EdgeScratch scr;
+    int64_t total;
 };
-StageWs slayout(int l, int n, int64_t b) {
+StageWs slayout(int l, int n, int64_t b, void* ws) {
     StageWs w{};
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    const int Cin = kCin[l], Cout = kCout[l];
-    w.wt = take((int64_t)2 * Cin * Cout * 4);
-    w.ws = take((int64_t)2 * Cin * Cout * 4);
-    w.P = take(b * 2 * Cout * NODES * 4);
-    w.part = take(cdiv(b, CHUNK) * Cout * 2 * 8);
-    w.sti = take((int64_t)2 * Cout * 8);
-    w.stat = take((int64_t)3 * Cout * 8);
-    w.dstat = take((int64_t)2 * Cout * 8);
-    w.rev_off = take(b * (NODES + 1) * 4);
-    w.rev = take(b * NODES * n * 4);
-    w.dP = take(b * 2 * Cout * NODES * 4);
-    w.wpart = take(wgrad_splits(b) * (int64_t)2 * Cout * Cin * 4);
-    w.arg = take(b * Cout * NODES);
-    w.total = o;
+    Carver c{ws};
+    w.edge = carve_edge(c, l, b);
+    w.scr = carve_scratch(c, b, kCout[l], 2 * kCout[l], n, (int64_t)2 * kCout[l] * kCin[l]);
+    w.total = c.used;
     return w;
 }
 int check_stage(int layer, int64_t b, int n) {
@@ -831,17 +799,18 @@ int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* be
     PCD_CHECK_ARG(w && gamma && beta && x && lists && out && argmax && stats, "a pointer is null");
     PCD_CHECK_ARG((running_mean != nullptr) == (running_var != nullptr), "running_mean and running_var go together");
     PCD_CHECK_ARG(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, "eps / momentum is invalid");
-    const int l = layer - 1, Cout = kCout[l];
+    const int l = layer - 1;
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
-    const StageWs s = slayout(l, list_len, b);
     char* ws;
-    PCD_HIP(tmp.alloc(&ws, s.total));
-    if ((rc = run_pack(w, l, at<float>(ws, s.wt), at<float>(ws, s.ws), st)) != PCD_OK) return rc;
-    const Bn bn{gamma, beta, running_mean, running_var, tracked, eps, momentum};
-    rc = edge_forward(l, at<float>(ws, s.wt), bn, x, (int64_t)kCin[l] * NODES, lists, list_len, at<float>(ws, s.P),
-                      at<double>(ws, s.part), stats, at<double>(ws, s.sti), out, (int64_t)Cout * NODES, argmax,
-                      (int64_t)Cout * NODES, b, st);
+    PCD_HIP(tmp.alloc(&ws, slayout(l, list_len, b, nullptr).total));
+    const StageWs sw = slayout(l, list_len, b, ws);
+    EdgeState s = sw.edge;
+    s.arg = argmax;          // the caller's, [b][Cout][64] as the carved ones are
+    s.stat = stats;
+    if ((rc = run_pack(w, l, s.Wt, s.Ws, st)) != PCD_OK) return rc;
+    const BnArgs bn = bn_params(gamma, beta, running_mean, running_var, tracked, eps, momentum);
+    rc = edge_forward(edge_layer_alone(l, x, lists, list_len), s, sw.scr, bn, out, b, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
@@ -854,27 +823,26 @@ int pcd_dgcnn_edgeconv_train_backward(const float* w, const float* gamma, const 
     if (rc != PCD_OK) return rc;
     PCD_CHECK_ARG(w && gamma && beta && x && lists && g && dab && dgamma && dbeta && dw, "a pointer is null");
     PCD_CHECK_ARG(eps >= 0.0, "eps is invalid");
-    const int l = layer - 1, Cin = kCin[l], Cout = kCout[l];
+    const int l = layer - 1;
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
-    const StageWs s = slayout(l, list_len, b);
     char* ws;
-    PCD_HIP(tmp.alloc(&ws, s.total + (int64_t)b * Cout * NODES * 4));
-    float* out = at<float>(ws, s.total);
-    if ((rc = run_pack(w, l, at<float>(ws, s.wt), at<float>(ws, s.ws), st)) != PCD_OK) return rc;
-    const Bn bn{gamma, beta, nullptr, nullptr, nullptr, eps, 0.0};
+    PCD_HIP(tmp.alloc(&ws, slayout(l, list_len, b, nullptr).total + (int64_t)b * kCout[l] * NODES * 4));
+    const StageWs sw = slayout(l, list_len, b, ws);
+    float* out = at<float>(ws, sw.total);
+    const EdgeLayer e = edge_layer_alone(l, x, lists, list_len);
+    const EdgeState& s = sw.edge;
+    EdgeScratch scr = sw.scr;
+    scr.dP = dab;            // the caller's
+    if ((rc = run_pack(w, l, s.Wt, s.Ws, st)) != PCD_OK) return rc;
+    const BnArgs bn = bn_params(gamma, beta, nullptr, nullptr, nullptr, eps, 0.0);
     // the forward again (no buffer is touched), then the backward on what it left
-    rc = edge_forward(l, at<float>(ws, s.wt), bn, x, (int64_t)Cin * NODES, lists, list_len, at<float>(ws, s.P),
-                      at<double>(ws, s.part), at<double>(ws, s.stat), at<double>(ws, s.sti), out, (int64_t)Cout * NODES,
-                      at<uint8_t>(ws, s.arg), (int64_t)Cout * NODES, b, st);
-    if (rc != PCD_OK) return rc;
-    if ((rc = run_reverse(lists, list_len, at<int32_t>(ws, s.rev_off), at<int32_t>(ws, s.rev), b, st)) != PCD_OK) return rc;
-    rc = edge_backward(l, at<float>(ws, s.ws), x, (int64_t)Cin * NODES, lists, list_len, at<int32_t>(ws, s.rev_off),
-                       at<int32_t>(ws, s.rev), at<float>(ws, s.P), at<uint8_t>(ws, s.arg), (int64_t)Cout * NODES, g,
-                       (int64_t)Cout * NODES, at<double>(ws, s.stat), at<double>(ws, s.sti), at<double>(ws, s.part),
-                       at<double>(ws, s.dstat), dab, at<float>(ws, s.wpart), dgamma, dbeta, dw, dx, (int64_t)Cin * NODES,
-                       false, b, st);
-    if (rc != PCD_OK) return rc;
+    if ((rc = edge_forward(e, s, scr, bn, out, b, st)) != PCD_OK) return rc;
+    if ((rc = run_reverse(lists, list_len, scr.rev_off, scr.rev, b, st)) != PCD_OK) return rc;
+    EdgeGrads gr{};
+    gr.g = g; gr.dX = dx; gr.add = false;
+    gr.dgamma = dgamma; gr.dbeta = dbeta; gr.dW = dw;
+    if ((rc = edge_backward(e, s, scr, gr, b, st)) != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
 }

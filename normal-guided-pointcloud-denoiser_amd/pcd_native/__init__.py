@@ -1322,8 +1322,8 @@ def dgcnn_train_forward(conv, bn, k: int, emb_dims: int, inputs: torch.Tensor, w
         raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(x.shape)}")
     b, dev = x.size(0), x.device
     prm = DgcnnTrainParams()
-    rows = [c for _, c in ((17, 64), (64, 64), (64, 128), (128, 256), (256, 256), (256, 256))] + [int(emb_dims)]
-    cols = [34, 128, 128, 256, 512, 512, 1024]
+    rows = list(DGCNN_COUT) + [int(emb_dims)]
+    cols = [2 * c for c in DGCNN_CIN] + [1024]
     for i, cw in enumerate(conv):
         if cw.numel() != rows[i] * cols[i] or cw.shape[0] != rows[i]:
             raise ValueError(f"pcd: conv{i + 1} weight must be [{rows[i]}, {cols[i]}], got {tuple(cw.shape)}")
