@@ -33,6 +33,15 @@
  *   pcd_dgcnn_train_* / _wgrad / _edgeconv_train(_backward)
  *                                   DGCNN.forward (train) and loss.backward()  PatchGeneration/Modules/Network/GCNModel.py:170-207
  *                                                                              PatchGeneration/Modules/NetworkController.py:120-136
+ *   pcd_bdgcnn_create / _destroy / _workspace_bytes
+ *                                   BetterDGCNN.__init__                       PatchGeneration/Modules/Network/GCNModel.py:217-256
+ *   pcd_bdgcnn_forward(_deferred)   BetterDGCNN.forward (eval)                 PatchGeneration/Modules/Network/GCNModel.py:258-297
+ *   pcd_bdgcnn_edgeconv(_scratch_bytes)
+ *                                   one edge layer of it: convN + max          PatchGeneration/Modules/Network/GCNModel.py:270-281
+ *   pcd_bdgcnn_train_workspace_bytes / _train_forward / _train_backward
+ *                                   BetterDGCNN.forward (train) up to the pooling, and loss.backward() below it
+ *                                                                              PatchGeneration/Modules/Network/GCNModel.py:258-287
+ *                                                                              PatchGeneration/Modules/NetworkController.py:120-136
  *   pcd_denoiser_*                  Processor.denoise / getMyFeatureDecomposition / denoiseUntilMinimumError loop body
  *                                                                              Pointcloud/Modules/Processor.py:110-185
  *   pcd_orient_normals_mst          GraphBuilder.flipNormals (MST + DFS, host) Pointcloud/Modules/GraphBuilder.py:129-209
@@ -566,6 +575,80 @@ int pcd_dgcnn_gemm(const float* w, const float* x, int m_rows, int k_cols, int64
                    const float* s, const float* t, float* y, void* stream);
 /* epilogue 4 of pcd_dgcnn_gemm: y += w . x, added into what y holds (the data gradients of the training step) */
 
+/* ------------------------------------------------------------------ BetterDGCNN (the layer table from the caller) */
+/* BetterDGCNN(l_e, l_d, l_l, channel_sizes, k, init_dims = 17, dropout, output_channels) of GCNModel.py:217-297: the
+ * network above with every count and width from the caller.  Convolution i (1-based, i <= l_e + l_d) is an edge
+ * convolution 2 C_{i-1} -> C_i with C_0 = 17 and C_i = channel_sizes[i - 1]; the first l_e run over the three index
+ * columns, the next l_d over the k nearest rows of their own input (with l_e = 0 the first search is on rows 0:17 of
+ * the input, and the index columns are never read nor checked).  Their outputs are concatenated ([Ccat][64], Ccat =
+ * C_1 + .. + C_{l_e + l_d}); convolution l_e + l_d + 1 maps Ccat -> C, followed by max and mean over the nodes; linear
+ * j < l_l maps C -> C' (input doubled for j = 1, a bias for j > 1) with batch norm l_e + l_d + 1 + j, the last linear
+ * channel_sizes[-1] -> output_channels.  The trunk's LeakyReLU slope is 0.2; the head's is F.leaky_relu's default
+ * 0.01 (GCNModel.py:291).  DGCNN is the table 3, 3, 4, [64, 64, 128, 256, 256, 256, emb, 512, 256, 64] with head slope
+ * 0.2, and runs through the same code.  The guarantees on bits are those of pcd_dgcnn_forward / pcd_dgcnn_train_*.
+ * Bounds (PCD_ERR_ARG naming the argument otherwise): l_e + l_d in [1, 16], l_l in [2, 16] (the reference fails
+ * outside the lower ones), channel_sizes[i] in [1, 4096] for the edge layers (so Ccat <= 65536) and [1, 65536] after
+ * them, k in [1, 64], init_dims = 17, output_channels in [1, 4096].  With them 2 Cin Cout <= 2^25 and every width times
+ * 64 nodes stay far inside int32; everything multiplied by the batch (b <= 2^20) is computed in int64. */
+#define PCD_DGCNN_MAX_EDGE_LAYERS 16
+#define PCD_DGCNN_MAX_LINEARS 16
+#define PCD_DGCNN_MAX_EDGE_WIDTH 4096
+#define PCD_DGCNN_MAX_WIDTH 65536
+#define PCD_BDGCNN_HEAD_SLOPE 0.01f
+typedef struct {
+    int32_t l_e, l_d, l_l;
+    const int32_t* channel_sizes;    /* HOST, [l_e + l_d + l_l] */
+    int32_t k, init_dims, output_channels;
+} pcd_dgcnn_table;
+typedef struct {
+    /* HOST arrays of the table's lengths; what they point to as in pcd_dgcnn_weights (HOST or DEVICE, row-major fp32).
+     * conv [l_e + l_d + 1]: [out][2 in], the last [C][Ccat]; batch norms [l_e + l_d + l_l]; linears [l_l] (lin_b[0]
+     * must be null). */
+    const float* const* conv_w;
+    const int32_t *conv_rows, *conv_cols;
+    const float* const* bn_weight;
+    const float* const* bn_bias;
+    const float* const* bn_mean;
+    const float* const* bn_var;
+    const double* bn_eps;
+    const int32_t* bn_len;
+    const float* const* lin_w;
+    const float* const* lin_b;
+    const int32_t *lin_rows, *lin_cols;
+} pcd_bdgcnn_weights;
+typedef struct {
+    /* optional DEVICE outputs (null: not wanted) */
+    float* cat;          /* [b][Ccat][64]                                                            */
+    int32_t* lists;      /* [l_d][b][64][k] the neighbour lists of the dynamic layers                */
+    float* pooled;       /* [b][2 C]                                                                 */
+    float* const* h;     /* HOST array of l_l - 1 DEVICE pointers: the hidden layers [width][b]      */
+} pcd_bdgcnn_debug;
+/* As pcd_dgcnn_create / _destroy / _workspace_bytes / _forward / _forward_deferred, for a table from the caller
+ * (BetterDGCNN.__init__ and .forward, GCNModel.py:217-297).  The handle is a pcd_dgcnn. */
+int pcd_bdgcnn_create(const pcd_dgcnn_table* table, const pcd_bdgcnn_weights* w, pcd_dgcnn** out);
+int pcd_bdgcnn_destroy(pcd_dgcnn* m);
+int pcd_bdgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes);
+int pcd_bdgcnn_forward(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                       int64_t workspace_bytes, const pcd_bdgcnn_debug* debug, void* stream);
+int pcd_bdgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                                int64_t workspace_bytes, const pcd_bdgcnn_debug* debug, int32_t* first_bad,
+                                int64_t patch_base, void* stream);
+/* Stage, for tests: one edge layer by (c_in, c_out) in eval() -- DEVICE w [c_out][2 c_in], the folded batch norm s, t
+ * [c_out], x [b][c_in][64], lists [b][64][list_len] (entries taken mod 64) -> out [b][c_out][64]
+ * (convN + max of GCNModel.py:270-281).  fused: PCD_FUSED_OFF runs the GEMM and the max over the lists as two kernels
+ * (DGCNN's path), PCD_FUSED_ON as one kernel that keeps the product in LDS -- the same bits; PCD_ERR_ARG unless
+ * 2 c_out <= 128, the GEMM's tile height -- and PCD_FUSED_AUTO as pcd_bdgcnn_forward chooses.  scratch: null -- the
+ * packed weight and the product come from the stream's memory pool and the call synchronises `stream`; or DEVICE
+ * memory, 16-byte aligned, of pcd_bdgcnn_edgeconv_scratch_bytes(c_in, c_out, b) bytes or more -- nothing is allocated
+ * and nothing waits (what tools/better_dgcnn_probe.py times). */
+#define PCD_FUSED_OFF 0
+#define PCD_FUSED_ON 1
+#define PCD_FUSED_AUTO 2
+int pcd_bdgcnn_edgeconv(const float* w, const float* s, const float* t, int c_in, int c_out, const float* x, int64_t b,
+                        const int32_t* lists, int list_len, int fused, float* out, void* scratch, int64_t scratch_bytes,
+                        void* stream);
+int pcd_bdgcnn_edgeconv_scratch_bytes(int c_in, int c_out, int64_t b, int64_t* bytes);
+
 /* ------------------------------------------------------------------ DGCNN training (train(), fp32) */
 /* conv1-7 and the max / mean pooling of DGCNN.forward with self.training (GCNModel.py:170-207): batch norms take the
  * batch's statistics (biased variance over every edge of the batch; sums in double, fixed order) and update their
@@ -627,6 +710,33 @@ int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* be
 int pcd_dgcnn_edgeconv_train_backward(const float* w, const float* gamma, const float* beta, double eps, int layer,
                                       const float* x, int64_t b, const int32_t* lists, int list_len, const float* g,
                                       float* dab, float* dgamma, float* dbeta, float* dw, float* dx, void* stream);
+/* The training step for a table from the caller (BetterDGCNN.forward with self.training, GCNModel.py:258-287, and
+ * loss.backward() below the pooling): as pcd_dgcnn_train_workspace_bytes / _forward / _backward, the arrays of
+ * l_e + l_d + 1 entries.  Batch statistics run over N = b x 64 x 3 edges in a static layer, b x 64 x k in a dynamic
+ * one and b x 64 in the pooled convolution.  lists: [l_d][b][64][k]. */
+typedef struct {
+    const float* const* conv_w;
+    const float* const* bn_weight;
+    const float* const* bn_bias;
+    float* const* bn_mean;
+    float* const* bn_var;
+    int64_t* const* bn_tracked;
+    const double* bn_eps;
+    const double* bn_momentum;
+} pcd_bdgcnn_train_params;
+typedef struct {
+    float* const* conv_w;
+    float* const* bn_weight;
+    float* const* bn_bias;
+} pcd_bdgcnn_train_grads;
+int pcd_bdgcnn_train_workspace_bytes(const pcd_dgcnn_table* table, int64_t b, int64_t* bytes);
+int pcd_bdgcnn_train_forward(const pcd_dgcnn_table* table, const pcd_bdgcnn_train_params* prm, const float* inputs,
+                             int64_t b, float* pooled, void* workspace, int64_t workspace_bytes, int32_t* lists,
+                             void* stream);
+/* pool_conv_w: the weight of convolution l_e + l_d + 1 the forward ran with */
+int pcd_bdgcnn_train_backward(const pcd_dgcnn_table* table, const float* inputs, int64_t b, const float* d_pooled,
+                              const float* pool_conv_w, void* workspace, int64_t workspace_bytes,
+                              const pcd_bdgcnn_train_grads* grads, void* stream);
 
 /* ------------------------------------------------------------------ normal orientation (host) */
 /* GraphBuilder.flipNormals: Kruskal MST on cost 1-|n_i·n_j| over the directed edge list (a[e] -> b[e],

@@ -1,7 +1,7 @@
 """Checkpoints and the training loop (drop-in for Network and NetworkTrainer of PatchGeneration/Modules/
 NetworkController.py).
 
-`Network(model)` holds a Network.GCNModel.DGCNN and saves / loads its state dict under the reference's `.t7` rules
+`Network(model)` holds a Network.GCNModel.DGCNN or BetterDGCNN and saves / loads its state dict under the reference's `.t7` rules
 (NetworkController.py:28-52).  `NetworkTrainer(network, batches).train(epochs, ...)` is the training half of
 NetworkTrainer.train (NetworkController.py:94-139): per batch `train()`, forward, the cosine and MSE losses weighted
 by `loss_based_on_value_loss`, `backward()`, one Adam step -- on a model built with `trainable=True`, whose
@@ -21,12 +21,12 @@ import torch.nn.functional as F
 
 import pcd_native as _nat
 
-from .Network.GCNModel import DGCNN
+from .Network.GCNModel import DGCNN, BetterDGCNN
 
 
 class Network:
     def __init__(self, model):
-        if not isinstance(model, DGCNN):
+        if not isinstance(model, DGCNN) and not isinstance(model, BetterDGCNN):
             raise ValueError("A Network is instantiated with a model that is not a member of DGCNN.\n"
                              f"Current type: {type(model)}")
         self.model = model

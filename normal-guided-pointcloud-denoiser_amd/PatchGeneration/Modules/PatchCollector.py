@@ -168,7 +168,8 @@ class PatchCollector:
         Mesh.denoise(guided_normals=...): (normals float64 [n, 3] on the device, number of fallbacks).
 
         Chunks of batch_faces patches go from iterNetworkInput (float32, channels first) through `model` (a
-        Network.GCNModel.DGCNN in eval(), on the device) with one workspace for all of them; each output o is taken
+        Network.GCNModel.DGCNN or BetterDGCNN in eval(), on the device) with one workspace for all of them, sized by
+        the model's own layer table (model.native().workspace); each output o is taken
         back with R^T o (PatchDataset.unalign's convention; the reference's NetworkController.py:257 computes R o) and
         normalised.  A face keeps its own normal -- and is counted -- where its patch is empty, does not hold the
         face (centre_index < 0), or the output is zero or not finite."""

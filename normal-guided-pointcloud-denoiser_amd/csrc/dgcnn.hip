@@ -1,4 +1,5 @@
-// The DGCNN forward pass (inference, fp32): GCNModel.py:121-215 of the reference as four kernels.
+// The DGCNN / BetterDGCNN forward pass (inference, fp32): GCNModel.py:121-297 of the reference as five kernels over a
+// runtime layer table (pcd_dgcnn.h: Net; DGCNN is the fixed instance of it).
 //
 //   gemm_kernel    Y = W . X on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per output), 128 x 64
 //                  tiles, W shared by all patches, X the patches' columns.  Epilogues: plain store, per-row affine
@@ -12,6 +13,8 @@
 //                  ascending, ties to the lower index (self included, as topk includes it).
 //   edge_kernel    out[c, i] = lrelu(max_j s_c (A[c, j] + B[c, i]) + t_c) over row i's list, where A = W_a X and
 //                  B = (W_b - W_a) X come from one GEMM: W [x_j - x_i ; x_i] = W_a x_j + (W_b - W_a) x_i.
+//   fused_edge_kernel   that GEMM and edge_kernel in one launch for a layer with 2 Cout <= 128: the patch's [A ; B]
+//                  tile stays in LDS (BetterDGCNN's narrow layers; DGCNN keeps the two kernels).  The same bits.
 //
 // Every output element depends on its own patch only and is summed in a fixed order: a patch's output bits do not
 // depend on the batch, its place in it, or the run.  No float atomics.  The library's -ffp-contract=off stays; where a
@@ -45,6 +48,7 @@ struct GemmArgs {
     float* pool_dbg;        // EPI_POOL, nullable: [b][2 M]
     int64_t N, G, xgs, xks, ygs, yms, b;
     int M, K, epi;
+    float slope;            // of the LeakyReLU epilogues
 };
 
 // max that keeps a NaN (torch's max does)
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             float v = acc[h][r];
             if (a.epi != EPI_PLAIN && a.epi != EPI_ADD && m < a.M) {
                 v = fmaf(a.s[m], v, a.t[m]);
-                if (a.epi != EPI_AFFINE) v = lrelu(v);
+                if (a.epi != EPI_AFFINE) v = lrelu(v, a.slope);
             }
             if (a.epi == EPI_POOL) {
                 Ps[rm * 65 + cn] = v;
@@ -265,8 +269,91 @@ __global__ __launch_bounds__(256) void edge_kernel(const float* P, int Cout, con
     out[p * ogs + (int64_t)c * NODES + i] = lrelu(m);
 }
 
+// A narrow edge layer (2 Cout <= BM) in one launch: workgroup p forms patch p's whole [A ; B] = Wt^T X tile as
+// gemm_kernel<0> does -- its k loop, statement for statement: the same fmaf chain per element -- stages it in LDS as
+// the pooling epilogue stages its tile, and applies edge_kernel's max over the lists from there.  P never reaches
+// memory; the output is edge_kernel's, bit for bit.
+struct FusedEdgeArgs {
+    const float* Wt;        // [Cin][2 Cout]
+    const float* X;         // [b][Cin][64], patch stride xgs
+    const int32_t* lists;   // [b][64][kk]
+    const float *s, *t;     // [Cout]
+    float* out;             // [b][Cout][64], patch stride ogs
+    int64_t xgs, ogs;
+    int Cin, Cout, kk;
+};
+
+__global__ __launch_bounds__(256) void fused_edge_kernel(FusedEdgeArgs a) {
+    __shared__ float lds[BM * 65];                     // the K tiles; afterwards the [BM][65] tile of P
+    __shared__ uint8_t nbr[NODES * NODES];             // the patch's lists [64][kk]
+    float* As = lds;
+    float* Bs = lds + BK * LDA;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;
+    const int64_t p = blockIdx.x;
+    const int M = 2 * a.Cout, K = a.Cin;
+    const int wcol = tid & 127, wrow0 = tid >> 7, xcol = tid & 63, xrow0 = tid >> 6;
+    const bool m_ok = wcol < M;
+    const float* Xp = a.X + p * a.xgs + xcol;
+    for (int e = tid; e < NODES * a.kk; e += 256) nbr[e] = (uint8_t)(a.lists[p * NODES * a.kk + e] & 63);
+    float wr[16], xr[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int k = k0 + wrow0 + 2 * r;
+            wr[r] = (m_ok && k < K) ? a.Wt[(int64_t)k * M + wcol] : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int k = k0 + xrow0 + 4 * r;
+            xr[r] = k < K ? Xp[(int64_t)k * NODES] : 0.f;
+        }
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+    fetch(0);
+    const int arow = lane >> 5, acol = lane & 31;
+    for (int k0 = 0; k0 < K; k0 += BK) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) As[(wrow0 + 2 * r) * LDA + wcol] = wr[r];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) Bs[(xrow0 + 4 * r) * LDB + xcol] = xr[r];
+        __syncthreads();
+        if (k0 + BK < K) fetch(k0 + BK);
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            const float a0 = As[(kk + arow) * LDA + wm + acol];
+            const float a1 = As[(kk + arow) * LDA + wm + 32 + acol];
+            const float bv = Bs[(kk + arow) * LDB + wn + acol];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, acc[1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // the tile to LDS: a lane's 16 registers are 16 rows of one column, so a wave's store covers 32 consecutive
+    // columns of two rows 4 apart -- 65 = 1 mod 32: no two lanes of a half-wave meet in a bank
+    float* Ps = lds;
+    const int cn = wn + acol;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ps[mfma_row(wm + 32 * h, r, arow) * 65 + cn] = acc[h][r];
+    __syncthreads();
+    // edge_kernel from LDS: lane = row i, a wave per channel, four channels a pass
+    const uint8_t* row = nbr + lane * a.kk;
+    for (int c = wave; c < a.Cout; c += 4) {
+        const float* A = Ps + c * 65;
+        const float Bi = Ps[(a.Cout + c) * 65 + lane];
+        const float sc = a.s[c], tc = a.t[c];
+        float m = -INFINITY;
+        for (int j = 0; j < a.kk; ++j) m = nanmax(m, fmaf(sc, A[row[j]] + Bi, tc));
+        a.out[p * a.ogs + (int64_t)c * NODES + lane] = lrelu(m);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- host side
-constexpr int kWideFlush = 8;        // k per float32 chain of the train-mode forward products
+constexpr int kWideFlush = 8;       // k per float32 chain of the train-mode forward products
 
 int launch_gemm(const GemmArgs& a, hipStream_t st, bool wide = false) {
     if (a.N <= 0 || a.M <= 0) return PCD_OK;
@@ -284,7 +371,7 @@ GemmArgs conv_args(const float* Wt, int M, int K, const float* X, int64_t xgs, f
     GemmArgs a{};
     a.Wt = Wt; a.X = X; a.Y = Y; a.M = M; a.K = K; a.b = b;
     a.N = b * NODES; a.G = NODES; a.xgs = xgs; a.xks = NODES; a.ygs = ygs; a.yms = NODES;
-    a.epi = EPI_PLAIN;
+    a.epi = EPI_PLAIN; a.slope = kTrunkSlope;
     return a;
 }
 // head form: X [K][b] -> Y [M][b]
@@ -292,56 +379,244 @@ GemmArgs head_args(const float* Wt, int M, int K, const float* X, float* Y, int6
     GemmArgs a{};
     a.Wt = Wt; a.X = X; a.Y = Y; a.M = M; a.K = K; a.b = b;
     a.N = b; a.G = b; a.xgs = 0; a.xks = b; a.ygs = 0; a.yms = b;
-    a.epi = EPI_PLAIN;
+    a.epi = EPI_PLAIN; a.slope = kTrunkSlope;
     return a;
 }
 
 }  // namespace
 
 struct pcd_dgcnn {
-    int k = 0, emb = 0, out_ch = 0;
+    Net net;
     float* dev = nullptr;          // every packed weight in one allocation
-    const float* wt[11] = {};      // transposed: 6 edge layers [Cin][2 Cout], conv7 [1024][emb], linear1-4
-    const float* s[11] = {};       // folded batch norms 1-10 (s, t); [10]: linear4 (1, bias)
-    const float* t[11] = {};
+    // transposed weights and folded batch norms (s, t), in network order: the E edge layers [Cin][2 Cout], the pooled
+    // convolution [Ccat][emb], the l_l linears; the last linear's (s, t) is (1, bias)
+    std::vector<const float*> wt, s, t;
 };
 
 namespace {
 
 struct Workspace {
-    float *cat, *P, *pooled, *h[3];   // [b][1024][64], [b][512][64], [2 emb][b], linear1-3's [kHead][b]
-    int32_t *idx3, *knn, *flag;       // [b][64][3], [3][b][64][k], [1]
+    float *cat, *P, *pooled;          // [b][Ccat][64], [b][2 product_rows][64], [2 emb][b]
+    float* h[kMaxLin];                // the head's hidden layers [width][b]
+    int32_t *idx3, *knn, *flag;       // [b][64][3], [l_d][b][64][k], [1]
     int64_t total;                    // bytes
 };
-Workspace layout(const pcd_dgcnn* m, int64_t b, void* ws) {
+// Where the fused kernel runs when the caller leaves the choice to the library (PCD_FUSED_AUTO): what
+// tools/better_dgcnn_probe.py measured -- faster than the two kernels at every list length from 3 to 64 for Cin from
+// 17 to 1024, by less the wider the input (1.4 x at Cin = 1024, k = 8).  Wider inputs were not measured and keep the
+// two kernels.
+constexpr int kFusedMaxCin = 1024;
+bool fused_wins(int Cin, int Cout, int /* kk */) { return 2 * Cout <= BM && Cin <= kFusedMaxCin; }
+bool fused_layer(const Net& n, int l) { return n.fuse && fused_wins(n.Cin[l], n.Cout[l], l < n.l_e ? 3 : n.k); }
+// the widest Cout whose [A ; B] product goes through memory (0: every layer is fused)
+int product_rows(const Net& n) {
+    int c = 0;
+    for (int l = 0; l < n.E; ++l)
+        if (!fused_layer(n, l) && n.Cout[l] > c) c = n.Cout[l];
+    return c;
+}
+
+Workspace layout(const Net& n, int64_t b, void* ws) {
     Workspace w{};
     Carver c{ws};
-    w.cat = c.carve<float>(b * 1024 * NODES * 4);
-    w.P = c.carve<float>(b * 512 * NODES * 4);
+    w.cat = c.carve<float>(b * n.cat_stride() * 4);
+    w.P = c.carve<float>(b * 2 * product_rows(n) * NODES * 4);
     w.idx3 = c.carve<int32_t>(b * NODES * 3 * 4);
-    w.knn = c.carve<int32_t>(3 * b * NODES * m->k * 4);
-    w.pooled = c.carve<float>(2 * (int64_t)m->emb * b * 4);
-    for (int l = 0; l < 3; ++l) w.h[l] = c.carve<float>(kHead[l] * b * 4);
+    w.knn = c.carve<int32_t>((int64_t)n.l_d * b * NODES * n.k * 4);
+    w.pooled = c.carve<float>(2 * (int64_t)n.emb * b * 4);
+    for (int l = 0; l + 1 < n.l_l; ++l) w.h[l] = c.carve<float>((int64_t)n.head[l] * b * 4);
     w.flag = c.carve<int32_t>(4);
     w.total = c.used;
     return w;
 }
 
-// out: the layer's output [b][Cout][64], patch stride e.ogs
-int run_edge(const pcd_dgcnn* m, int layer, const EdgeLayer& e, float* P, float* out, int64_t b, hipStream_t st) {
-    const int rc = launch_gemm(conv_args(m->wt[layer], 2 * e.Cout, e.Cin, e.X, e.xgs, P, (int64_t)2 * e.Cout * NODES, b), st);
+// out: the layer's output [b][Cout][64], patch stride e.ogs.  fused: P is not touched.
+int run_edge(const float* wt, const float* s, const float* t, const EdgeLayer& e, float* P, float* out, int64_t b,
+             bool fused, hipStream_t st) {
+    if (fused) {
+        FusedEdgeArgs a{wt, e.X, e.lists, s, t, out, e.xgs, e.ogs, e.Cin, e.Cout, e.kk};
+        hipLaunchKernelGGL(fused_edge_kernel, dim3((unsigned)b), dim3(256), 0, st, a);
+        PCD_LAUNCH_CHECK();
+        return PCD_OK;
+    }
+    const int rc = launch_gemm(conv_args(wt, 2 * e.Cout, e.Cin, e.X, e.xgs, P, (int64_t)2 * e.Cout * NODES, b), st);
     if (rc != PCD_OK) return rc;
     hipLaunchKernelGGL(edge_kernel, dim3((unsigned)b, (unsigned)cdiv(e.Cout, 4)), dim3(256), 0, st, P, e.Cout, e.lists,
-                       e.kk, m->s[layer], m->t[layer], out, e.ogs);
+                       e.kk, s, t, out, e.ogs);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
 }
+
+// the weights of either create entry: arrays of the table's lengths
+struct WeightView {
+    const float* const* conv_w;  const int32_t *conv_rows, *conv_cols;                      // [E + 1]
+    const float *const *bn_weight, *const *bn_bias, *const *bn_mean, *const *bn_var;        // [E + l_l - 1]
+    const double* bn_eps;  const int32_t* bn_len;
+    const float *const *lin_w, *const *lin_b;  const int32_t *lin_rows, *lin_cols;          // [l_l]
+};
+
+int create_impl(const Net& n, const WeightView& w, pcd_dgcnn** out) {
+    const int E = n.E, L = n.l_l, nb = n.nbn();    // batch norms: E + 1 convolutions, L - 1 hidden linears
+    // the shapes of the layer table
+    std::vector<int> cr(E + 1), cc(E + 1), bl(nb), lr(L), lc(L);
+    for (int l = 0; l < E; ++l) { cr[l] = n.Cout[l]; cc[l] = 2 * n.Cin[l]; bl[l] = n.Cout[l]; }
+    cr[E] = n.emb; cc[E] = n.Ccat; bl[E] = n.emb;
+    for (int l = 0; l < L; ++l) { lr[l] = n.out_of_linear(l); lc[l] = n.in_of_linear(l); }
+    for (int l = 0; l + 1 < L; ++l) bl[E + 1 + l] = n.head[l];
+    for (int l = 0; l <= E; ++l) {
+        PCD_CHECK_ARG(w.conv_w[l] != nullptr, "conv" + std::to_string(l + 1) + " weight is null");
+        PCD_CHECK_ARG(w.conv_rows[l] == cr[l] && w.conv_cols[l] == cc[l],
+                      "conv" + std::to_string(l + 1) + " weight must be [" + std::to_string(cr[l]) + ", " +
+                          std::to_string(cc[l]) + "], got [" + std::to_string(w.conv_rows[l]) + ", " +
+                          std::to_string(w.conv_cols[l]) + "]");
+    }
+    for (int l = 0; l < nb; ++l) {
+        PCD_CHECK_ARG(w.bn_weight[l] && w.bn_bias[l] && w.bn_mean[l] && w.bn_var[l],
+                      "bn" + std::to_string(l + 1) + " has a null pointer");
+        PCD_CHECK_ARG(w.bn_len[l] == bl[l], "bn" + std::to_string(l + 1) + " must have " + std::to_string(bl[l]) +
+                                                " channels, got " + std::to_string(w.bn_len[l]));
+        PCD_CHECK_ARG(w.bn_eps[l] >= 0.0 && w.bn_eps[l] == w.bn_eps[l], "bn" + std::to_string(l + 1) + " eps is invalid");
+    }
+    for (int l = 0; l < L; ++l) {
+        PCD_CHECK_ARG(w.lin_w[l] != nullptr, "linear" + std::to_string(l + 1) + " weight is null");
+        PCD_CHECK_ARG(w.lin_rows[l] == lr[l] && w.lin_cols[l] == lc[l],
+                      "linear" + std::to_string(l + 1) + " weight must be [" + std::to_string(lr[l]) + ", " +
+                          std::to_string(lc[l]) + "], got [" + std::to_string(w.lin_rows[l]) + ", " +
+                          std::to_string(w.lin_cols[l]) + "]");
+        PCD_CHECK_ARG((w.lin_b[l] != nullptr) == (l > 0),
+                      l == 0 ? std::string("linear1 has no bias") : "linear" + std::to_string(l + 1) + " bias is null");
+    }
+    // everything to the host (the pointers may be host or device memory), folded in double, rounded once
+    auto pull = [](const float* src, int64_t cnt, std::vector<float>& dst) {
+        dst.resize(cnt);
+        return hipMemcpy(dst.data(), src, cnt * sizeof(float), hipMemcpyDefault);
+    };
+    const int total = E + 1 + L;
+    std::vector<float> packed;
+    std::vector<int64_t> wt_off(total), s_off(total), t_off(total);
+    std::vector<float> W, g, be, mu, var, bias;
+    // batch norm l -> (s, t) at slot `at`
+    auto fold = [&](int l, int at, const std::vector<float>* lin_bias) {
+        const int cnt = bl[l];
+        s_off[at] = (int64_t)packed.size();
+        for (int c = 0; c < cnt; ++c) packed.push_back((float)((double)g[c] / sqrt((double)var[c] + w.bn_eps[l])));
+        t_off[at] = (int64_t)packed.size();
+        for (int c = 0; c < cnt; ++c) {
+            const double sc = (double)g[c] / sqrt((double)var[c] + w.bn_eps[l]);
+            const double shift = (lin_bias ? (double)(*lin_bias)[c] : 0.0) - (double)mu[c];
+            packed.push_back((float)((double)be[c] + sc * shift));
+        }
+    };
+    auto pull_bn = [&](int l) -> hipError_t {
+        hipError_t e = pull(w.bn_weight[l], bl[l], g);
+        if (e == hipSuccess) e = pull(w.bn_bias[l], bl[l], be);
+        if (e == hipSuccess) e = pull(w.bn_mean[l], bl[l], mu);
+        if (e == hipSuccess) e = pull(w.bn_var[l], bl[l], var);
+        return e;
+    };
+    for (int l = 0; l <= E; ++l) {
+        PCD_HIP(pull(w.conv_w[l], (int64_t)cr[l] * cc[l], W));
+        PCD_HIP(pull_bn(l));
+        wt_off[l] = (int64_t)packed.size();
+        if (l < E) {                                   // [W_a ; W_b - W_a], transposed to [Cin][2 Cout]
+            const int Cin = n.Cin[l], Cout = n.Cout[l];
+            for (int kq = 0; kq < Cin; ++kq) {
+                for (int c = 0; c < Cout; ++c) packed.push_back(W[(int64_t)c * 2 * Cin + kq]);
+                for (int c = 0; c < Cout; ++c)
+                    packed.push_back((float)((double)W[(int64_t)c * 2 * Cin + Cin + kq] - (double)W[(int64_t)c * 2 * Cin + kq]));
+            }
+        } else {
+            for (int kq = 0; kq < n.Ccat; ++kq)
+                for (int c = 0; c < n.emb; ++c) packed.push_back(W[(int64_t)c * n.Ccat + kq]);
+        }
+        fold(l, l, nullptr);
+    }
+    for (int l = 0; l < L; ++l) {
+        const int at = E + 1 + l;
+        PCD_HIP(pull(w.lin_w[l], (int64_t)lr[l] * lc[l], W));
+        if (l > 0) PCD_HIP(pull(w.lin_b[l], lr[l], bias));
+        wt_off[at] = (int64_t)packed.size();
+        for (int kq = 0; kq < lc[l]; ++kq)
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(W[(int64_t)c * lc[l] + kq]);
+        if (l + 1 < L) {
+            PCD_HIP(pull_bn(at));
+            fold(at, at, l > 0 ? &bias : nullptr);
+        } else {
+            s_off[at] = (int64_t)packed.size();
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(1.f);
+            t_off[at] = (int64_t)packed.size();
+            for (int c = 0; c < lr[l]; ++c) packed.push_back(bias[c]);
+        }
+    }
+    pcd_dgcnn* m = new pcd_dgcnn();
+    m->net = n;
+    hipError_t e = hipMalloc((void**)&m->dev, packed.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(m->dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (m->dev) (void)hipFree(m->dev);
+        delete m;
+        return fail(e == hipErrorOutOfMemory ? PCD_ERR_OOM : PCD_ERR_HIP,
+                    std::string("pcd_dgcnn_create: ") + hipGetErrorString(e));
+    }
+    m->wt.resize(total); m->s.resize(total); m->t.resize(total);
+    for (int l = 0; l < total; ++l) {
+        m->wt[l] = m->dev + wt_off[l];
+        m->s[l] = m->dev + s_off[l];
+        m->t[l] = m->dev + t_off[l];
+    }
+    *out = m;
+    return PCD_OK;
+}
+
+// what a debug struct of either entry asks for
+struct DebugView {
+    float* cat;  int32_t* lists;  float* pooled;
+    float* h[kMaxLin];
+};
 
 }  // namespace
 
 // the launchers csrc/dgcnn_train.hip uses too (declared in pcd_dgcnn.h)
 namespace pcd {
 namespace dgcnn {
+
+int make_net(Net* n, int l_e, int l_d, int l_l, const int* cs, int k, int init_dims, int output_channels,
+             float head_slope) {
+    PCD_CHECK_ARG(l_e >= 0 && l_d >= 0, "l_e and l_d must be >= 0");
+    PCD_CHECK_ARG(l_e <= kMaxEdge && l_d <= kMaxEdge && l_e + l_d >= 1 && l_e + l_d <= kMaxEdge,
+                  "l_e + l_d must be in [1, " + std::to_string(kMaxEdge) + "] (there is nothing to concatenate without an "
+                  "edge layer), got " + std::to_string(l_e) + " + " + std::to_string(l_d));
+    PCD_CHECK_ARG(l_l >= 2 && l_l <= kMaxLin, "l_l must be in [2, " + std::to_string(kMaxLin) + "] (the last linear reads "
+                  "channel_sizes[-1], a hidden width), got " + std::to_string(l_l));
+    PCD_CHECK_ARG(cs != nullptr, "channel_sizes is null");
+    PCD_CHECK_ARG(init_dims == 17, "init_dims must be 17 (the network's forward slices rows 0:17 of its input)");
+    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
+    PCD_CHECK_ARG(output_channels >= 1 && output_channels <= 4096, "output_channels must be in [1, 4096]");
+    *n = Net{};
+    n->l_e = l_e; n->l_d = l_d; n->l_l = l_l; n->E = l_e + l_d; n->k = k; n->out_ch = output_channels;
+    n->head_slope = head_slope;
+    for (int i = 0; i < n->E + l_l; ++i) {
+        const int lim = i < n->E ? kMaxEdgeWidth : kMaxWidth;
+        PCD_CHECK_ARG(cs[i] >= 1 && cs[i] <= lim, "channel_sizes[" + std::to_string(i) + "] must be in [1, " +
+                                                      std::to_string(lim) + "], got " + std::to_string(cs[i]));
+    }
+    for (int l = 0; l < n->E; ++l) {
+        n->Cin[l] = l == 0 ? 17 : cs[l - 1];
+        n->Cout[l] = cs[l];
+        n->cat_off[l] = n->Ccat;
+        n->Ccat += cs[l];
+        n->Cmax = cs[l] > n->Cmax ? cs[l] : n->Cmax;
+    }
+    n->emb = cs[n->E];
+    for (int j = 0; j + 1 < l_l; ++j) n->head[j] = cs[n->E + 1 + j];
+    return PCD_OK;
+}
+
+int fixed_net(Net* n, int k, int emb, int output_channels) {
+    PCD_CHECK_ARG(emb >= 1 && emb <= (1 << 16), "emb_dims must be in [1, 65536]");
+    const int cs[10] = {64, 64, 128, 256, 256, 256, emb, 512, 256, 64};
+    return make_net(n, 3, 3, 4, cs, k, 17, output_channels, 0.2f);
+}
 
 int conv_gemm(const float* Wt, int M, int K, const float* X, int64_t xgs, float* Y, int64_t ygs, int64_t b, int epi,
               bool wide, hipStream_t st) {
@@ -382,6 +657,92 @@ int transpose(const float* W, int M, int K, float* Wt, hipStream_t st) {
 }  // namespace dgcnn
 }  // namespace pcd
 
+// first_bad null: the index flag lives in the workspace, is read after the index kernel (one stream synchronise) and
+// a bad index column refuses the call.  Otherwise the caller's device flag takes atomicMin(patch_base + patch), the
+// clamped indices are used and nothing waits for the device.  A table without static layers (l_e = 0) never reads the
+// index columns: they are not checked.
+static int forward_impl(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                        int64_t workspace_bytes, const DebugView* debug, int32_t* first_bad, int64_t patch_base,
+                        void* stream) {
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(inputs != nullptr && out != nullptr, "inputs / out is null");
+    const Net& n = m->net;
+    const Workspace w = layout(n, b, workspace);
+    PCD_CHECK_ARG(workspace != nullptr && workspace_bytes >= w.total,
+                  "workspace of " + std::to_string(workspace_bytes) + " bytes is shorter than the " +
+                      std::to_string(w.total) + " that " + (n.fuse ? "pcd_bdgcnn_workspace_bytes" : "pcd_dgcnn_workspace_bytes") +
+                      " asks for");
+    PCD_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+    PCD_CHECK_ARG(patch_base >= 0 && patch_base + b < kNoBadPatch, "patch_base + b must be in [0, 0x7f7f7f7f)");
+    hipStream_t st = as_stream(stream);
+
+    // the index columns first: a bad one ends the call before anything is computed from it (or, deferred, is
+    // recorded in the caller's flag while the clamped index is used)
+    int rc;
+    if (n.l_e > 0 && first_bad) {
+        if ((rc = index_lists(inputs, b, w.idx3, first_bad, (int)patch_base, st)) != PCD_OK) return rc;
+    } else if (n.l_e > 0) {
+        int bad;
+        if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
+        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
+                                          " has an index column (rows 17:20) outside [0, 63] or NaN; no output written");
+    }
+
+    const int E = n.E;
+    for (int l = 0; l < E; ++l) {
+        const EdgeLayer e = edge_layer(n, l, inputs, w.cat, w.idx3, w.knn, b);
+        if (e.knn && (rc = dgcnn::knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
+        const bool fused = fused_layer(n, l);
+        if ((rc = run_edge(m->wt[l], m->s[l], m->t[l], e, w.P, w.cat + e.out_off, b, fused, st)) != PCD_OK) return rc;
+    }
+    {   // the pooled convolution + batch norm + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
+        GemmArgs a = conv_args(m->wt[E], n.emb, n.Ccat, w.cat, n.cat_stride(), nullptr, 0, b);
+        a.epi = EPI_POOL; a.s = m->s[E]; a.t = m->t[E]; a.poolT = w.pooled;
+        a.pool_dbg = debug ? debug->pooled : nullptr;
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+    }
+    const int H = n.l_l - 1;                            // hidden linears
+    for (int l = 0; l < H; ++l) {
+        GemmArgs a = head_args(m->wt[E + 1 + l], n.head[l], n.in_of_linear(l), l ? w.h[l - 1] : w.pooled, w.h[l], b);
+        a.epi = EPI_AFFINE_LRELU; a.s = m->s[E + 1 + l]; a.t = m->t[E + 1 + l]; a.slope = n.head_slope;
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+    }
+    {   // the last linear (+ bias) -> out [b][out_ch]
+        GemmArgs a = head_args(m->wt[E + 1 + H], n.out_ch, n.head[H - 1], w.h[H - 1], out, b);
+        a.G = 1; a.ygs = n.out_ch; a.yms = 1;           // Y(m, n) = out[n * out_ch + m]
+        a.xgs = 1; a.xks = b;                           // X(k, n) = h[k * b + n]
+        a.epi = EPI_AFFINE; a.s = m->s[E + 1 + H]; a.t = m->t[E + 1 + H];
+        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
+    }
+    if (debug) {
+        if (debug->cat) PCD_HIP(hipMemcpyAsync(debug->cat, w.cat, b * n.cat_stride() * 4, hipMemcpyDeviceToDevice, st));
+        if (debug->lists && n.l_d > 0)
+            PCD_HIP(hipMemcpyAsync(debug->lists, w.knn, (int64_t)n.l_d * b * NODES * n.k * 4, hipMemcpyDeviceToDevice, st));
+        for (int l = 0; l < H; ++l)
+            if (debug->h[l])
+                PCD_HIP(hipMemcpyAsync(debug->h[l], w.h[l], (int64_t)n.head[l] * b * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return PCD_OK;
+}
+
+static bool fixed_debug(const pcd_dgcnn_debug* d, DebugView* v) {
+    if (!d) return false;
+    *v = DebugView{};
+    v->cat = d->cat; v->lists = d->lists; v->pooled = d->pooled;
+    v->h[0] = d->h1; v->h[1] = d->h2; v->h[2] = d->h3;
+    return true;
+}
+static bool table_debug(const pcd_dgcnn* m, const pcd_bdgcnn_debug* d, DebugView* v) {
+    if (!d) return false;
+    *v = DebugView{};
+    v->cat = d->cat; v->lists = d->lists; v->pooled = d->pooled;
+    if (m && d->h)
+        for (int l = 0; l + 1 < m->net.l_l; ++l) v->h[l] = d->h[l];
+    return true;
+}
+
 extern "C" {
 
 int pcd_dgcnn_create(const pcd_dgcnn_weights* w, int k, int init_dims, int emb_dims, int output_channels,
@@ -390,114 +751,30 @@ int pcd_dgcnn_create(const pcd_dgcnn_weights* w, int k, int init_dims, int emb_d
     *out = nullptr;
     PCD_CHECK_ARG(w != nullptr, "weights is null");
     PCD_CHECK_ARG(init_dims == 17, "init_dims must be 17 (the network's forward slices rows 0:17 of its input)");
-    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
-    PCD_CHECK_ARG(emb_dims >= 1 && emb_dims <= (1 << 16), "emb_dims must be in [1, 65536]");
-    PCD_CHECK_ARG(output_channels >= 1 && output_channels <= 4096, "output_channels must be in [1, 4096]");
-    // the shapes of the layer table
-    int cr[7], cc[7], bl[10], lr[4], lc[4];
-    for (int l = 0; l < 6; ++l) { cr[l] = kCout[l]; cc[l] = 2 * kCin[l]; bl[l] = kCout[l]; }
-    cr[6] = emb_dims; cc[6] = 1024; bl[6] = emb_dims;
-    for (int l = 0; l < 3; ++l) { lr[l] = bl[7 + l] = kHead[l]; lc[l] = l ? kHead[l - 1] : 2 * emb_dims; }
-    lr[3] = output_channels; lc[3] = kHead[2];
-    for (int l = 0; l < 7; ++l) {
-        PCD_CHECK_ARG(w->conv_w[l] != nullptr, "conv" + std::to_string(l + 1) + " weight is null");
-        PCD_CHECK_ARG(w->conv_rows[l] == cr[l] && w->conv_cols[l] == cc[l],
-                      "conv" + std::to_string(l + 1) + " weight must be [" + std::to_string(cr[l]) + ", " +
-                          std::to_string(cc[l]) + "], got [" + std::to_string(w->conv_rows[l]) + ", " +
-                          std::to_string(w->conv_cols[l]) + "]");
-    }
-    for (int l = 0; l < 10; ++l) {
-        PCD_CHECK_ARG(w->bn_weight[l] && w->bn_bias[l] && w->bn_mean[l] && w->bn_var[l],
-                      "bn" + std::to_string(l + 1) + " has a null pointer");
-        PCD_CHECK_ARG(w->bn_len[l] == bl[l], "bn" + std::to_string(l + 1) + " must have " + std::to_string(bl[l]) +
-                                                 " channels, got " + std::to_string(w->bn_len[l]));
-        PCD_CHECK_ARG(w->bn_eps[l] >= 0.0 && w->bn_eps[l] == w->bn_eps[l], "bn" + std::to_string(l + 1) + " eps is invalid");
-    }
-    for (int l = 0; l < 4; ++l) {
-        PCD_CHECK_ARG(w->lin_w[l] != nullptr, "linear" + std::to_string(l + 1) + " weight is null");
-        PCD_CHECK_ARG(w->lin_rows[l] == lr[l] && w->lin_cols[l] == lc[l],
-                      "linear" + std::to_string(l + 1) + " weight must be [" + std::to_string(lr[l]) + ", " +
-                          std::to_string(lc[l]) + "], got [" + std::to_string(w->lin_rows[l]) + ", " +
-                          std::to_string(w->lin_cols[l]) + "]");
-        PCD_CHECK_ARG((w->lin_b[l] != nullptr) == (l > 0),
-                      l == 0 ? std::string("linear1 has no bias") : "linear" + std::to_string(l + 1) + " bias is null");
-    }
-    // everything to the host (the pointers may be host or device memory), folded in double, rounded once
-    auto pull = [](const float* src, int64_t n, std::vector<float>& dst) {
-        dst.resize(n);
-        return hipMemcpy(dst.data(), src, n * sizeof(float), hipMemcpyDefault);
-    };
-    std::vector<float> packed;
-    int64_t wt_off[11], s_off[11], t_off[11];
-    std::vector<float> W, g, be, mu, var, bias;
-    auto fold = [&](int l, const std::vector<float>* lin_bias) {     // batch norm l -> (s, t)
-        const int n = bl[l];
-        s_off[l] = (int64_t)packed.size();
-        for (int c = 0; c < n; ++c) packed.push_back((float)((double)g[c] / sqrt((double)var[c] + w->bn_eps[l])));
-        t_off[l] = (int64_t)packed.size();
-        for (int c = 0; c < n; ++c) {
-            const double sc = (double)g[c] / sqrt((double)var[c] + w->bn_eps[l]);
-            const double shift = (lin_bias ? (double)(*lin_bias)[c] : 0.0) - (double)mu[c];
-            packed.push_back((float)((double)be[c] + sc * shift));
-        }
-    };
-    auto pull_bn = [&](int l) -> hipError_t {
-        hipError_t e = pull(w->bn_weight[l], bl[l], g);
-        if (e == hipSuccess) e = pull(w->bn_bias[l], bl[l], be);
-        if (e == hipSuccess) e = pull(w->bn_mean[l], bl[l], mu);
-        if (e == hipSuccess) e = pull(w->bn_var[l], bl[l], var);
-        return e;
-    };
-    for (int l = 0; l < 7; ++l) {
-        PCD_HIP(pull(w->conv_w[l], (int64_t)cr[l] * cc[l], W));
-        PCD_HIP(pull_bn(l));
-        wt_off[l] = (int64_t)packed.size();
-        if (l < 6) {                                   // [W_a ; W_b - W_a], transposed to [Cin][2 Cout]
-            const int Cin = kCin[l], Cout = kCout[l];
-            for (int kq = 0; kq < Cin; ++kq) {
-                for (int c = 0; c < Cout; ++c) packed.push_back(W[(int64_t)c * 2 * Cin + kq]);
-                for (int c = 0; c < Cout; ++c)
-                    packed.push_back((float)((double)W[(int64_t)c * 2 * Cin + Cin + kq] - (double)W[(int64_t)c * 2 * Cin + kq]));
-            }
-        } else {
-            for (int kq = 0; kq < 1024; ++kq)
-                for (int c = 0; c < emb_dims; ++c) packed.push_back(W[(int64_t)c * 1024 + kq]);
-        }
-        fold(l, nullptr);
-    }
-    for (int l = 0; l < 4; ++l) {
-        PCD_HIP(pull(w->lin_w[l], (int64_t)lr[l] * lc[l], W));
-        if (l > 0) PCD_HIP(pull(w->lin_b[l], lr[l], bias));
-        wt_off[7 + l] = (int64_t)packed.size();
-        for (int kq = 0; kq < lc[l]; ++kq)
-            for (int c = 0; c < lr[l]; ++c) packed.push_back(W[(int64_t)c * lc[l] + kq]);
-        if (l < 3) {
-            PCD_HIP(pull_bn(7 + l));
-            fold(7 + l, l > 0 ? &bias : nullptr);
-        } else {
-            s_off[10] = (int64_t)packed.size();
-            for (int c = 0; c < lr[l]; ++c) packed.push_back(1.f);
-            t_off[10] = (int64_t)packed.size();
-            for (int c = 0; c < lr[l]; ++c) packed.push_back(bias[c]);
-        }
-    }
-    pcd_dgcnn* m = new pcd_dgcnn();
-    m->k = k; m->emb = emb_dims; m->out_ch = output_channels;
-    hipError_t e = hipMalloc((void**)&m->dev, packed.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(m->dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->dev) (void)hipFree(m->dev);
-        delete m;
-        return fail(e == hipErrorOutOfMemory ? PCD_ERR_OOM : PCD_ERR_HIP,
-                    std::string("pcd_dgcnn_create: ") + hipGetErrorString(e));
-    }
-    for (int l = 0; l < 11; ++l) {
-        m->wt[l] = m->dev + wt_off[l];
-        m->s[l] = m->dev + s_off[l];
-        m->t[l] = m->dev + t_off[l];
-    }
-    *out = m;
-    return PCD_OK;
+    Net n;
+    const int rc = fixed_net(&n, k, emb_dims, output_channels);
+    if (rc != PCD_OK) return rc;
+    const WeightView v{w->conv_w, w->conv_rows, w->conv_cols, w->bn_weight, w->bn_bias, w->bn_mean, w->bn_var,
+                       w->bn_eps, w->bn_len, w->lin_w, w->lin_b, w->lin_rows, w->lin_cols};
+    return create_impl(n, v, out);
+}
+
+int pcd_bdgcnn_create(const pcd_dgcnn_table* t, const pcd_bdgcnn_weights* w, pcd_dgcnn** out) {
+    PCD_CHECK_ARG(out != nullptr, "out is null");
+    *out = nullptr;
+    PCD_CHECK_ARG(t != nullptr, "table is null");
+    Net n;
+    const int rc = make_net(&n, t->l_e, t->l_d, t->l_l, t->channel_sizes, t->k, t->init_dims, t->output_channels,
+                            PCD_BDGCNN_HEAD_SLOPE);
+    if (rc != PCD_OK) return rc;
+    n.fuse = true;
+    PCD_CHECK_ARG(w != nullptr, "weights is null");
+    PCD_CHECK_ARG(w->conv_w && w->conv_rows && w->conv_cols && w->bn_weight && w->bn_bias && w->bn_mean && w->bn_var &&
+                      w->bn_eps && w->bn_len && w->lin_w && w->lin_b && w->lin_rows && w->lin_cols,
+                  "weights has a null array");
+    const WeightView v{w->conv_w, w->conv_rows, w->conv_cols, w->bn_weight, w->bn_bias, w->bn_mean, w->bn_var,
+                       w->bn_eps, w->bn_len, w->lin_w, w->lin_b, w->lin_rows, w->lin_cols};
+    return create_impl(n, v, out);
 }
 
 int pcd_dgcnn_destroy(pcd_dgcnn* m) {
@@ -506,89 +783,49 @@ int pcd_dgcnn_destroy(pcd_dgcnn* m) {
     delete m;
     return PCD_OK;
 }
+int pcd_bdgcnn_destroy(pcd_dgcnn* m) { return pcd_dgcnn_destroy(m); }
 
 int pcd_dgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes) {
     PCD_CHECK_ARG(m != nullptr, "model is null");
     PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
-    *bytes = layout(m, b, nullptr).total;
+    *bytes = layout(m->net, b, nullptr).total;
     return PCD_OK;
 }
-
-// first_bad null: the index flag lives in the workspace, is read after the index kernel (one stream synchronise) and
-// a bad index column refuses the call.  Otherwise the caller's device flag takes atomicMin(patch_base + patch), the
-// clamped indices are used and nothing waits for the device.
-static int forward_impl(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
-                        int64_t workspace_bytes, const pcd_dgcnn_debug* debug, int32_t* first_bad, int64_t patch_base,
-                        void* stream) {
-    PCD_CHECK_ARG(m != nullptr, "model is null");
-    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
-    if (b == 0) return PCD_OK;
-    PCD_CHECK_ARG(inputs != nullptr && out != nullptr, "inputs / out is null");
-    const Workspace w = layout(m, b, workspace);
-    PCD_CHECK_ARG(workspace != nullptr && workspace_bytes >= w.total,
-                  "workspace of " + std::to_string(workspace_bytes) + " bytes is shorter than the " +
-                      std::to_string(w.total) + " that pcd_dgcnn_workspace_bytes asks for");
-    PCD_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
-    PCD_CHECK_ARG(patch_base >= 0 && patch_base + b < kNoBadPatch, "patch_base + b must be in [0, 0x7f7f7f7f)");
-    hipStream_t st = as_stream(stream);
-
-    // the index columns first: a bad one ends the call before anything is computed from it (or, deferred, is
-    // recorded in the caller's flag while the clamped index is used)
-    int rc;
-    if (first_bad) {
-        if ((rc = index_lists(inputs, b, w.idx3, first_bad, (int)patch_base, st)) != PCD_OK) return rc;
-    } else {
-        int bad;
-        if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
-        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
-                                          " has an index column (rows 17:20) outside [0, 63] or NaN; no output written");
-    }
-
-    for (int l = 0; l < 6; ++l) {
-        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, m->k, b);
-        if (e.knn && (rc = dgcnn::knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
-        if ((rc = run_edge(m, l, e, w.P, w.cat + e.out_off, b, st)) != PCD_OK) return rc;
-    }
-    {   // conv7 + bn7 + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
-        GemmArgs a = conv_args(m->wt[6], m->emb, 1024, w.cat, kCatStride, nullptr, 0, b);
-        a.epi = EPI_POOL; a.s = m->s[6]; a.t = m->t[6]; a.poolT = w.pooled;
-        a.pool_dbg = debug ? debug->pooled : nullptr;
-        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
-    }
-    for (int l = 0; l < 3; ++l) {
-        GemmArgs a = head_args(m->wt[7 + l], kHead[l], l ? kHead[l - 1] : 2 * m->emb, l ? w.h[l - 1] : w.pooled, w.h[l], b);
-        a.epi = EPI_AFFINE_LRELU; a.s = m->s[7 + l]; a.t = m->t[7 + l];
-        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
-    }
-    {   // linear4 (+ bias) -> out [b][out_ch]
-        GemmArgs a = head_args(m->wt[10], m->out_ch, 64, w.h[2], out, b);
-        a.G = 1; a.ygs = m->out_ch; a.yms = 1;          // Y(m, n) = out[n * out_ch + m]
-        a.xgs = 1; a.xks = b;                           // X(k, n) = h3[k * b + n]
-        a.epi = EPI_AFFINE; a.s = m->s[10]; a.t = m->t[10];
-        if ((rc = launch_gemm(a, st)) != PCD_OK) return rc;
-    }
-    if (debug) {
-        if (debug->cat) PCD_HIP(hipMemcpyAsync(debug->cat, w.cat, b * kCatStride * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->lists)
-            PCD_HIP(hipMemcpyAsync(debug->lists, w.knn, 3 * b * NODES * m->k * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h1) PCD_HIP(hipMemcpyAsync(debug->h1, w.h[0], 512 * b * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h2) PCD_HIP(hipMemcpyAsync(debug->h2, w.h[1], 256 * b * 4, hipMemcpyDeviceToDevice, st));
-        if (debug->h3) PCD_HIP(hipMemcpyAsync(debug->h3, w.h[2], 64 * b * 4, hipMemcpyDeviceToDevice, st));
-    }
-    return PCD_OK;
+int pcd_bdgcnn_workspace_bytes(const pcd_dgcnn* m, int64_t b, int64_t* bytes) {
+    return pcd_dgcnn_workspace_bytes(m, b, bytes);
 }
 
 int pcd_dgcnn_forward(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
                       int64_t workspace_bytes, const pcd_dgcnn_debug* debug, void* stream) {
-    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, debug, nullptr, 0, stream);
+    DebugView v;
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, fixed_debug(debug, &v) ? &v : nullptr, nullptr, 0,
+                        stream);
 }
 
 int pcd_dgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
                                int64_t workspace_bytes, const pcd_dgcnn_debug* debug, int32_t* first_bad,
                                int64_t patch_base, void* stream) {
     PCD_CHECK_ARG(first_bad != nullptr, "first_bad is null");
-    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, debug, first_bad, patch_base, stream);
+    DebugView v;
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, fixed_debug(debug, &v) ? &v : nullptr, first_bad,
+                        patch_base, stream);
+}
+
+int pcd_bdgcnn_forward(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                       int64_t workspace_bytes, const pcd_bdgcnn_debug* debug, void* stream) {
+    DebugView v;
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, table_debug(m, debug, &v) ? &v : nullptr, nullptr,
+                        0, stream);
+}
+
+int pcd_bdgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t b, float* out, void* workspace,
+                                int64_t workspace_bytes, const pcd_bdgcnn_debug* debug, int32_t* first_bad,
+                                int64_t patch_base, void* stream) {
+    PCD_CHECK_ARG(first_bad != nullptr, "first_bad is null");
+    DebugView v;
+    return forward_impl(m, inputs, b, out, workspace, workspace_bytes, table_debug(m, debug, &v) ? &v : nullptr,
+                        first_bad, patch_base, stream);
 }
 
 int pcd_dgcnn_knn(const float* x, int64_t b, int channels, int k, int32_t* lists, void* stream) {
@@ -603,19 +840,73 @@ int pcd_dgcnn_knn(const float* x, int64_t b, int channels, int k, int32_t* lists
 int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b, const int32_t* lists, int list_len,
                        float* out, void* stream) {
     PCD_CHECK_ARG(m != nullptr, "model is null");
-    PCD_CHECK_ARG(layer >= 1 && layer <= 6, "layer must be in [1, 6]");
+    PCD_CHECK_ARG(layer >= 1 && layer <= m->net.E, "layer must be in [1, " + std::to_string(m->net.E) + "]");
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
     PCD_CHECK_ARG(list_len >= 1 && list_len <= NODES, "list_len must be in [1, 64]");
     if (b == 0) return PCD_OK;
     PCD_CHECK_ARG(x != nullptr && lists != nullptr && out != nullptr, "x / lists / out is null");
-    const int l = layer - 1;
+    const int l = layer - 1, Cin = m->net.Cin[l], Cout = m->net.Cout[l];
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
     float* P;
-    PCD_HIP(tmp.alloc(&P, b * 2 * kCout[l] * NODES * sizeof(float)));
-    const int rc = run_edge(m, l, edge_layer_alone(l, x, lists, list_len), P, out, b, st);
+    PCD_HIP(tmp.alloc(&P, b * 2 * Cout * NODES * sizeof(float)));
+    const int rc = run_edge(m->wt[l], m->s[l], m->t[l], edge_layer_alone(Cin, Cout, x, lists, list_len), P, out, b, false, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+// the stage entry's scratch: the packed weight [c_in][2 c_out], then (two kernels) P [b][2 c_out][64]
+static int64_t edgeconv_scratch(int c_in, int c_out, int64_t b, bool fused, void* base, float** wt, float** P) {
+    Carver c{base};
+    *wt = c.carve<float>((int64_t)2 * c_in * c_out * 4);
+    *P = fused ? nullptr : c.carve<float>(b * 2 * c_out * NODES * 4);
+    return c.used;
+}
+
+int pcd_bdgcnn_edgeconv_scratch_bytes(int c_in, int c_out, int64_t b, int64_t* bytes) {
+    PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
+    PCD_CHECK_ARG(c_in >= 1 && c_in <= kMaxEdgeWidth && c_out >= 1 && c_out <= kMaxEdgeWidth,
+                  "c_in and c_out must be in [1, " + std::to_string(kMaxEdgeWidth) + "]");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    float *wt, *P;
+    *bytes = edgeconv_scratch(c_in, c_out, b, false, nullptr, &wt, &P);
+    return PCD_OK;
+}
+
+int pcd_bdgcnn_edgeconv(const float* w, const float* s, const float* t, int c_in, int c_out, const float* x, int64_t b,
+                        const int32_t* lists, int list_len, int fused, float* out, void* scratch, int64_t scratch_bytes,
+                        void* stream) {
+    PCD_CHECK_ARG(fused == PCD_FUSED_OFF || fused == PCD_FUSED_ON || fused == PCD_FUSED_AUTO,
+                  "fused must be PCD_FUSED_OFF, PCD_FUSED_ON or PCD_FUSED_AUTO");
+    PCD_CHECK_ARG(fused != PCD_FUSED_ON || 2 * c_out <= BM,
+                  "fused = PCD_FUSED_ON needs 2 c_out <= " + std::to_string(BM) + " (one GEMM tile holds the patch's [A ; B])");
+    PCD_CHECK_ARG(c_in >= 1 && c_in <= kMaxEdgeWidth && c_out >= 1 && c_out <= kMaxEdgeWidth,
+                  "c_in and c_out must be in [1, " + std::to_string(kMaxEdgeWidth) + "]");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(list_len >= 1 && list_len <= NODES, "list_len must be in [1, 64]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(w && s && t && x && lists && out, "a pointer is null");
+    const bool fuse = fused == PCD_FUSED_ON || (fused == PCD_FUSED_AUTO && fused_wins(c_in, c_out, list_len));
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    float *wt, *P;
+    const int64_t need = edgeconv_scratch(c_in, c_out, b, fuse, scratch, &wt, &P);
+    if (scratch) {
+        PCD_CHECK_ARG(scratch_bytes >= need && reinterpret_cast<uintptr_t>(scratch) % 16 == 0,
+                      "scratch must be 16-byte aligned and hold the " + std::to_string(need) +
+                          " bytes that pcd_bdgcnn_edgeconv_scratch_bytes asks for at most, got " +
+                          std::to_string(scratch_bytes));
+    } else {
+        char* own;
+        PCD_HIP(tmp.alloc(&own, need));
+        edgeconv_scratch(c_in, c_out, b, fuse, own, &wt, &P);
+    }
+    int rc = dgcnn::pack_edge(w, c_in, c_out, wt, nullptr, st);
+    if (rc != PCD_OK) return rc;
+    rc = run_edge(wt, s, t, edge_layer_alone(c_in, c_out, x, lists, list_len), P, out, b, fuse, st);
+    if (rc != PCD_OK) return rc;
+    if (!scratch) PCD_HIP(tmp.release());
     return PCD_OK;
 }
 

@@ -59,7 +59,7 @@ __device__ __forceinline__ void put_partial(double* part, int C, int c, double s
     }
 }
 
-// W [Cout][2 Cin] -> Wt [Cin][2 Cout] and Ws [2 Cout][Cin] of [W_a ; W_b - W_a]
+// W [Cout][2 Cin] -> Wt [Cin][2 Cout] and Ws [2 Cout][Cin] (null: not wanted) of [W_a ; W_b - W_a]
 __global__ void pack_edge_kernel(const float* W, int Cin, int Cout, float* Wt, float* Ws) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= Cin * Cout) return;
@@ -68,8 +68,10 @@ __global__ void pack_edge_kernel(const float* W, int Cin, int Cout, float* Wt, f
     const float wd = W[(int64_t)c * 2 * Cin + Cin + k] - wa;
     Wt[(int64_t)k * 2 * Cout + c] = wa;
     Wt[(int64_t)k * 2 * Cout + Cout + c] = wd;
-    Ws[(int64_t)c * Cin + k] = wa;
-    Ws[(int64_t)(Cout + c) * Cin + k] = wd;
+    if (Ws) {
+        Ws[(int64_t)c * Cin + k] = wa;
+        Ws[(int64_t)(Cout + c) * Cin + k] = wd;
+    }
 }
 
 // part [chunk][C][2]: sum and sum of squares of y over the chunk's edges (lane = row i, a wave per channel)
@@ -549,17 +551,9 @@ int run_reverse(const int32_t* lists, int kk, int32_t* rev_off, int32_t* rev, in
     return PCD_OK;
 }
 
-int run_pack(const float* W, int l, float* Wt, float* Ws, hipStream_t st) {
-    hipLaunchKernelGGL(pack_edge_kernel, dim3((unsigned)cdiv(kCin[l] * kCout[l], 256)), dim3(256), 0, st, W, kCin[l], kCout[l],
-                       Wt, Ws);
-    PCD_LAUNCH_CHECK();
-    return PCD_OK;
-}
-
 // The whole step (TrainWs) and the single-layer stage entries (StageWs) carve their per-layer state and the shared
 // scratch with the same two functions.
-EdgeState carve_edge(Carver& c, int l, int64_t b) {
-    const int Cin = kCin[l], Cout = kCout[l];
+EdgeState carve_edge(Carver& c, int Cin, int Cout, int64_t b) {
     EdgeState s{};
     s.Wt = c.carve<float>((int64_t)2 * Cin * Cout * 4);
     s.Ws = c.carve<float>((int64_t)2 * Cin * Cout * 4);
@@ -583,39 +577,47 @@ EdgeScratch carve_scratch(Carver& c, int64_t b, int C, int P_rows, int kk, int64
 }
 
 struct TrainWs {
-    EdgeState edge[6];
+    EdgeState edge[kMaxEdge];
     EdgeScratch scr;
-    float *w7t, *cat, *dcat; // conv7's weight transposed [1024][emb]; the concatenation [b][1024][64] and its gradient
-    float* Y7;               // [b][emb][64]: conv7's product, then its gradient
-    uint8_t* arg7;           // [b][emb]
-    double *stat7, *sti7;    // as an edge layer's
-    int32_t *idx3, *knn, *flag;   // [b][64][3], [3][b][64][k], [1]
+    float *wpt, *cat, *dcat; // the pooled convolution's weight transposed [Ccat][emb]; the concatenation [b][Ccat][64]
+                             // and its gradient
+    float* Yp;               // [b][emb][64]: the pooled convolution's product, then its gradient
+    uint8_t* argp;           // [b][emb]
+    double *statp, *stip;    // as an edge layer's
+    int32_t *idx3, *knn, *flag;   // [b][64][3], [l_d][b][64][k], [1]
     int64_t total;           // bytes
 };
-TrainWs tlayout(int k, int emb, int64_t b, void* ws) {
+TrainWs tlayout(const Net& n, int64_t b, void* ws) {
     TrainWs w{};
     Carver c{ws};
-    for (int l = 0; l < 6; ++l) w.edge[l] = carve_edge(c, l, b);
-    w.w7t = c.carve<float>((int64_t)1024 * emb * 4);
-    w.cat = c.carve<float>(b * 1024 * NODES * 4);
-    w.dcat = c.carve<float>(b * 1024 * NODES * 4);
+    int64_t wfloats = (int64_t)n.emb * n.Ccat;
+    for (int l = 0; l < n.E; ++l) {
+        w.edge[l] = carve_edge(c, n.Cin[l], n.Cout[l], b);
+        wfloats = std::max(wfloats, (int64_t)2 * n.Cout[l] * n.Cin[l]);
+    }
+    w.wpt = c.carve<float>((int64_t)n.Ccat * n.emb * 4);
+    w.cat = c.carve<float>(b * n.cat_stride() * 4);
+    w.dcat = c.carve<float>(b * n.cat_stride() * 4);
     w.idx3 = c.carve<int32_t>(b * NODES * 3 * 4);
-    w.knn = c.carve<int32_t>(3 * b * NODES * k * 4);
-    w.Y7 = c.carve<float>(b * emb * NODES * 4);
-    w.arg7 = c.carve<uint8_t>(b * emb);
-    w.stat7 = c.carve<double>((int64_t)3 * emb * 8);
-    w.sti7 = c.carve<double>((int64_t)2 * emb * 8);
-    w.scr = carve_scratch(c, b, std::max(256, emb), 512, std::max(3, k), std::max<int64_t>((int64_t)emb * 1024, 512 * 256));
+    w.knn = c.carve<int32_t>((int64_t)n.l_d * b * NODES * n.k * 4);
+    w.Yp = c.carve<float>(b * n.emb * NODES * 4);
+    w.argp = c.carve<uint8_t>(b * n.emb);
+    w.statp = c.carve<double>((int64_t)3 * n.emb * 8);
+    w.stip = c.carve<double>((int64_t)2 * n.emb * 8);
+    w.scr = carve_scratch(c, b, std::max(n.Cmax, n.emb), 2 * n.Cmax, std::max(3, n.k), wfloats);
     w.flag = c.carve<int32_t>(4);
     w.total = c.used;
     return w;
 }
 
-int check_dims(int k, int emb, int64_t b) {
-    PCD_CHECK_ARG(k >= 1 && k <= NODES, "k must be in [1, 64]");
-    PCD_CHECK_ARG(emb >= 1 && emb <= (1 << 16), "emb_dims must be in [1, 65536]");
+int check_batch(int64_t b) {
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
     return PCD_OK;
+}
+int table_net(const pcd_dgcnn_table* t, Net* n) {
+    PCD_CHECK_ARG(t != nullptr, "table is null");
+    return make_net(n, t->l_e, t->l_d, t->l_l, t->channel_sizes, t->k, t->init_dims, t->output_channels,
+                    PCD_BDGCNN_HEAD_SLOPE);
 }
 
 int check_ws(const TrainWs& w, const void* workspace, int64_t bytes) {
@@ -626,121 +628,205 @@ int check_ws(const TrainWs& w, const void* workspace, int64_t bytes) {
     return PCD_OK;
 }
 
+// the parameters and gradients of either entry: arrays of E + 1
+struct ParamView {
+    const float *const *conv_w, *const *bn_weight, *const *bn_bias;
+    float *const *bn_mean, *const *bn_var;
+    int64_t* const* bn_tracked;
+    const double *bn_eps, *bn_momentum;
+};
+struct GradView {
+    float *const *conv_w, *const *bn_weight, *const *bn_bias;
+};
+
+int train_forward_impl(const Net& n, const ParamView& prm, const float* inputs, int64_t b, float* pooled,
+                       void* workspace, int64_t workspace_bytes, int32_t* lists_out, void* stream) {
+    int rc = check_batch(b);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(b >= 1, "b must be >= 1 (batch statistics of an empty batch do not exist)");
+    PCD_CHECK_ARG(inputs != nullptr && pooled != nullptr, "inputs / pooled is null");
+    const int E = n.E, emb = n.emb;
+    for (int l = 0; l <= E; ++l) {
+        const std::string name = std::to_string(l + 1);
+        PCD_CHECK_ARG(prm.conv_w[l] != nullptr, "conv" + name + " weight is null");
+        PCD_CHECK_ARG(prm.bn_weight[l] != nullptr && prm.bn_bias[l] != nullptr, "bn" + name + " weight / bias is null");
+        PCD_CHECK_ARG((prm.bn_mean[l] != nullptr) == (prm.bn_var[l] != nullptr),
+                      "bn" + name + ": running_mean and running_var go together");
+        PCD_CHECK_ARG(prm.bn_eps[l] >= 0.0, "bn" + name + " eps is invalid");
+        PCD_CHECK_ARG(prm.bn_momentum[l] >= 0.0 && prm.bn_momentum[l] <= 1.0, "bn" + name + " momentum must be in [0, 1]");
+    }
+    const TrainWs w = tlayout(n, b, workspace);
+    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
+    hipStream_t st = as_stream(stream);
+
+    // the index columns first: a bad one ends the call before anything is computed or a buffer updated (a table
+    // without static layers never reads them)
+    if (n.l_e > 0) {
+        int bad;
+        if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
+        PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
+                                          " has an index column (rows 17:20) outside [0, 63] or NaN; nothing written");
+    }
+    for (int l = 0; l < E; ++l)
+        if ((rc = pack_edge(prm.conv_w[l], n.Cin[l], n.Cout[l], w.edge[l].Wt, w.edge[l].Ws, st)) != PCD_OK) return rc;
+    if ((rc = transpose(prm.conv_w[E], emb, n.Ccat, w.wpt, st)) != PCD_OK) return rc;
+
+    auto bn_of = [&](int l) {
+        return bn_params(prm.bn_weight[l], prm.bn_bias[l], prm.bn_mean[l], prm.bn_var[l], prm.bn_tracked[l],
+                         prm.bn_eps[l], prm.bn_momentum[l]);
+    };
+    for (int l = 0; l < E; ++l) {
+        const EdgeLayer e = edge_layer(n, l, inputs, w.cat, w.idx3, w.knn, b);
+        if (e.knn && (rc = knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
+        if ((rc = edge_forward(e, w.edge[l], w.scr, bn_of(l), w.cat + e.out_off, b, st)) != PCD_OK) return rc;
+    }
+    {   // the pooled convolution: the product is stored (the backward turns it into dY in place), then statistics and
+        // pooling
+        rc = conv_gemm(w.wpt, emb, n.Ccat, w.cat, n.cat_stride(), w.Yp, (int64_t)emb * NODES, b, EPI_PLAIN, true, st);
+        if (rc != PCD_OK) return rc;
+        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb, 4));
+        hipLaunchKernelGGL(row_stats_kernel, chunks, dim3(256), 0, st, w.Yp, emb, b, w.scr.part);
+        PCD_LAUNCH_CHECK();
+        rc = run_finalize(bn_of(E), w.scr.part, b, emb, (double)b * NODES, w.statp, w.stip, st);
+        if (rc != PCD_OK) return rc;
+        hipLaunchKernelGGL(pool_train_kernel, dim3((unsigned)b, (unsigned)cdiv(emb, 4)), dim3(256), 0, st, w.Yp, emb,
+                           w.stip, pooled, w.argp);
+        PCD_LAUNCH_CHECK();
+    }
+    if (lists_out && n.l_d > 0)
+        PCD_HIP(hipMemcpyAsync(lists_out, w.knn, (int64_t)n.l_d * b * NODES * n.k * 4, hipMemcpyDeviceToDevice, st));
+    return PCD_OK;
+}
+
+int train_backward_impl(const Net& n, const float* inputs, int64_t b, const float* d_pooled, const float* pool_w,
+                        void* workspace, int64_t workspace_bytes, const GradView& grads, void* stream) {
+    int rc = check_batch(b);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(b >= 1, "b must be >= 1");
+    PCD_CHECK_ARG(inputs != nullptr && d_pooled != nullptr && pool_w != nullptr,
+                  "inputs / d_pooled / the pooled convolution's weight is null");
+    const int E = n.E, emb = n.emb;
+    for (int l = 0; l <= E; ++l)
+        PCD_CHECK_ARG(grads.conv_w[l] && grads.bn_weight[l] && grads.bn_bias[l],
+                      "gradient " + std::to_string(l + 1) + " has a null pointer");
+    const TrainWs w = tlayout(n, b, workspace);
+    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    const EdgeScratch& scr = w.scr;
+    {   // the pooled convolution: pooling, LeakyReLU and batch norm, dY in place of the stored product
+        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb, 4));
+        hipLaunchKernelGGL(pool_bwd_reduce_kernel, chunks, dim3(256), 0, st, w.Yp, emb, w.argp, d_pooled, w.statp, w.stip, b,
+                           scr.part);
+        PCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(emb, 64)), dim3(64), 0, st, scr.part,
+                           (int)cdiv(b, CHUNK), emb, scr.dstat, grads.bn_weight[E], grads.bn_bias[E]);
+        PCD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pool_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(emb, 4)), dim3(256), 0, st, w.Yp, emb,
+                           w.argp, d_pooled, w.statp, w.stip, scr.dstat, 1.0 / ((double)b * NODES));
+        PCD_LAUNCH_CHECK();
+        // dcat = W^T dY: W [emb][Ccat] itself is the GEMM's transposed operand; every slice's first contribution
+        rc = conv_gemm(pool_w, n.Ccat, emb, w.Yp, (int64_t)emb * NODES, w.dcat, n.cat_stride(), b, EPI_PLAIN, false, st);
+        if (rc != PCD_OK) return rc;
+        WgradArgs a{};
+        a.dY = w.Yp; a.ygs = (int64_t)emb * NODES; a.M = emb;
+        a.X = w.cat; a.xgs = n.cat_stride(); a.K = n.Ccat; a.part = scr.wpart;
+        if ((rc = run_wgrad(a, b, grads.conv_w[E], 0, st)) != PCD_OK) return rc;
+    }
+    const int32_t* reversed = nullptr;   // the lists scr.rev holds: the static layers share theirs
+    for (int l = E - 1; l >= 0; --l) {
+        const EdgeLayer e = edge_layer(n, l, inputs, w.cat, w.idx3, w.knn, b);
+        if (e.lists != reversed) {
+            if ((rc = run_reverse(e.lists, e.kk, scr.rev_off, scr.rev, b, st)) != PCD_OK) return rc;
+            reversed = e.lists;
+        }
+        // the gradient of a slice of cat is that slice of dcat, which already holds the pooled convolution's
+        // contribution: this layer's is added second.  The network's inputs take none.
+        EdgeGrads gr{};
+        gr.g = w.dcat + e.out_off; gr.dX = e.X == inputs ? nullptr : w.dcat + (e.X - w.cat); gr.add = true;
+        gr.dgamma = grads.bn_weight[l]; gr.dbeta = grads.bn_bias[l]; gr.dW = grads.conv_w[l];
+        if ((rc = edge_backward(e, w.edge[l], scr, gr, b, st)) != PCD_OK) return rc;
+    }
+    return PCD_OK;
+}
+
 }  // namespace
+
+namespace pcd {
+namespace dgcnn {
+int pack_edge(const float* W, int Cin, int Cout, float* Wt, float* Ws, hipStream_t st) {
+    hipLaunchKernelGGL(pack_edge_kernel, dim3((unsigned)cdiv(Cin * Cout, 256)), dim3(256), 0, st, W, Cin, Cout, Wt, Ws);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+}  // namespace dgcnn
+}  // namespace pcd
 
 extern "C" {
 
 int pcd_dgcnn_train_workspace_bytes(int k, int emb_dims, int64_t b, int64_t* bytes) {
     PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
-    const int rc = check_dims(k, emb_dims, b);
-    if (rc != PCD_OK) return rc;
-    *bytes = tlayout(k, emb_dims, b, nullptr).total;
+    Net n;
+    int rc = fixed_net(&n, k, emb_dims, 1);
+    if (rc != PCD_OK || (rc = check_batch(b)) != PCD_OK) return rc;
+    *bytes = tlayout(n, b, nullptr).total;
     return PCD_OK;
 }
 
 int pcd_dgcnn_train_forward(const pcd_dgcnn_train_params* prm, int k, int emb_dims, const float* inputs, int64_t b,
                             float* pooled, void* workspace, int64_t workspace_bytes, int32_t* lists_out, void* stream) {
     PCD_CHECK_ARG(prm != nullptr, "params is null");
-    int rc = check_dims(k, emb_dims, b);
+    Net n;
+    const int rc = fixed_net(&n, k, emb_dims, 1);
     if (rc != PCD_OK) return rc;
-    PCD_CHECK_ARG(b >= 1, "b must be >= 1 (batch statistics of an empty batch do not exist)");
-    PCD_CHECK_ARG(inputs != nullptr && pooled != nullptr, "inputs / pooled is null");
-    for (int l = 0; l < 7; ++l) {
-        const std::string name = std::to_string(l + 1);
-        PCD_CHECK_ARG(prm->conv_w[l] != nullptr, "conv" + name + " weight is null");
-        PCD_CHECK_ARG(prm->bn_weight[l] != nullptr && prm->bn_bias[l] != nullptr, "bn" + name + " weight / bias is null");
-        PCD_CHECK_ARG((prm->bn_mean[l] != nullptr) == (prm->bn_var[l] != nullptr),
-                      "bn" + name + ": running_mean and running_var go together");
-        PCD_CHECK_ARG(prm->bn_eps[l] >= 0.0, "bn" + name + " eps is invalid");
-        PCD_CHECK_ARG(prm->bn_momentum[l] >= 0.0 && prm->bn_momentum[l] <= 1.0, "bn" + name + " momentum must be in [0, 1]");
-    }
-    const TrainWs w = tlayout(k, emb_dims, b, workspace);
-    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
-    hipStream_t st = as_stream(stream);
-
-    // the index columns first: a bad one ends the call before anything is computed or a buffer updated
-    int bad;
-    if ((rc = index_lists_checked(inputs, b, w.idx3, w.flag, &bad, st)) != PCD_OK) return rc;
-    PCD_CHECK_ARG(bad == kNoBadPatch, "patch " + std::to_string(bad) +
-                                      " has an index column (rows 17:20) outside [0, 63] or NaN; nothing written");
-    for (int l = 0; l < 6; ++l)
-        if ((rc = run_pack(prm->conv_w[l], l, w.edge[l].Wt, w.edge[l].Ws, st)) != PCD_OK) return rc;
-    if ((rc = transpose(prm->conv_w[6], emb_dims, 1024, w.w7t, st)) != PCD_OK) return rc;
-
-    auto bn_of = [&](int l) {
-        return bn_params(prm->bn_weight[l], prm->bn_bias[l], prm->bn_mean[l], prm->bn_var[l], prm->bn_tracked[l],
-                         prm->bn_eps[l], prm->bn_momentum[l]);
-    };
-    for (int l = 0; l < 6; ++l) {
-        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, k, b);
-        if (e.knn && (rc = knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
-        if ((rc = edge_forward(e, w.edge[l], w.scr, bn_of(l), w.cat + e.out_off, b, st)) != PCD_OK) return rc;
-    }
-    {   // conv7: the product is stored (the backward turns it into dY in place), then statistics and pooling
-        rc = conv_gemm(w.w7t, emb_dims, 1024, w.cat, kCatStride, w.Y7, (int64_t)emb_dims * NODES, b, EPI_PLAIN, true, st);
-        if (rc != PCD_OK) return rc;
-        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
-        hipLaunchKernelGGL(row_stats_kernel, chunks, dim3(256), 0, st, w.Y7, emb_dims, b, w.scr.part);
-        PCD_LAUNCH_CHECK();
-        rc = run_finalize(bn_of(6), w.scr.part, b, emb_dims, (double)b * NODES, w.stat7, w.sti7, st);
-        if (rc != PCD_OK) return rc;
-        hipLaunchKernelGGL(pool_train_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, w.Y7,
-                           emb_dims, w.sti7, pooled, w.arg7);
-        PCD_LAUNCH_CHECK();
-    }
-    if (lists_out) PCD_HIP(hipMemcpyAsync(lists_out, w.knn, 3 * b * NODES * k * 4, hipMemcpyDeviceToDevice, st));
-    return PCD_OK;
+    const ParamView v{prm->conv_w, prm->bn_weight, prm->bn_bias, prm->bn_mean, prm->bn_var, prm->bn_tracked, prm->bn_eps,
+                      prm->bn_momentum};
+    return train_forward_impl(n, v, inputs, b, pooled, workspace, workspace_bytes, lists_out, stream);
 }
 
 int pcd_dgcnn_train_backward(int k, int emb_dims, const float* inputs, int64_t b, const float* d_pooled,
                              const float* conv7_w, void* workspace, int64_t workspace_bytes,
                              const pcd_dgcnn_train_grads* grads, void* stream) {
-    int rc = check_dims(k, emb_dims, b);
+    Net n;
+    const int rc = fixed_net(&n, k, emb_dims, 1);
     if (rc != PCD_OK) return rc;
-    PCD_CHECK_ARG(b >= 1, "b must be >= 1");
-    PCD_CHECK_ARG(inputs != nullptr && d_pooled != nullptr && conv7_w != nullptr, "inputs / d_pooled / conv7_w is null");
     PCD_CHECK_ARG(grads != nullptr, "grads is null");
-    for (int l = 0; l < 7; ++l)
-        PCD_CHECK_ARG(grads->conv_w[l] && grads->bn_weight[l] && grads->bn_bias[l],
-                      "gradient " + std::to_string(l + 1) + " has a null pointer");
-    const TrainWs w = tlayout(k, emb_dims, b, workspace);
-    if ((rc = check_ws(w, workspace, workspace_bytes)) != PCD_OK) return rc;
-    hipStream_t st = as_stream(stream);
-    const EdgeScratch& scr = w.scr;
-    {   // conv7: pooling, LeakyReLU and batch norm, dY in place of the stored product
-        const dim3 chunks((unsigned)cdiv(b, CHUNK), (unsigned)cdiv(emb_dims, 4));
-        hipLaunchKernelGGL(pool_bwd_reduce_kernel, chunks, dim3(256), 0, st, w.Y7, emb_dims, w.arg7, d_pooled, w.stat7,
-                           w.sti7, b, scr.part);
-        PCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(emb_dims, 64)), dim3(64), 0, st, scr.part,
-                           (int)cdiv(b, CHUNK), emb_dims, scr.dstat, grads->bn_weight[6], grads->bn_bias[6]);
-        PCD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pool_bwd_apply_kernel, dim3((unsigned)b, (unsigned)cdiv(emb_dims, 4)), dim3(256), 0, st, w.Y7,
-                           emb_dims, w.arg7, d_pooled, w.stat7, w.sti7, scr.dstat, 1.0 / ((double)b * NODES));
-        PCD_LAUNCH_CHECK();
-        // dcat = W7^T dY: W7 [emb][1024] itself is the GEMM's transposed operand; every slice's first contribution
-        rc = conv_gemm(conv7_w, 1024, emb_dims, w.Y7, (int64_t)emb_dims * NODES, w.dcat, kCatStride, b, EPI_PLAIN, false, st);
-        if (rc != PCD_OK) return rc;
-        WgradArgs a{};
-        a.dY = w.Y7; a.ygs = (int64_t)emb_dims * NODES; a.M = emb_dims;
-        a.X = w.cat; a.xgs = kCatStride; a.K = 1024; a.part = scr.wpart;
-        if ((rc = run_wgrad(a, b, grads->conv_w[6], 0, st)) != PCD_OK) return rc;
-    }
-    const int32_t* reversed = nullptr;   // the lists scr.rev holds: layers 1-3 share theirs
-    for (int l = 5; l >= 0; --l) {
-        const EdgeLayer e = edge_layer(l, inputs, w.cat, w.idx3, w.knn, k, b);
-        if (e.lists != reversed) {
-            if ((rc = run_reverse(e.lists, e.kk, scr.rev_off, scr.rev, b, st)) != PCD_OK) return rc;
-            reversed = e.lists;
-        }
-        // the gradient of a slice of cat is that slice of dcat, which already holds conv7's contribution: this
-        // layer's is added second.  The network's inputs take none.
-        EdgeGrads gr{};
-        gr.g = w.dcat + e.out_off; gr.dX = e.X == inputs ? nullptr : w.dcat + (e.X - w.cat); gr.add = true;
-        gr.dgamma = grads->bn_weight[l]; gr.dbeta = grads->bn_bias[l]; gr.dW = grads->conv_w[l];
-        if ((rc = edge_backward(e, w.edge[l], scr, gr, b, st)) != PCD_OK) return rc;
-    }
+    const GradView v{grads->conv_w, grads->bn_weight, grads->bn_bias};
+    return train_backward_impl(n, inputs, b, d_pooled, conv7_w, workspace, workspace_bytes, v, stream);
+}
+
+int pcd_bdgcnn_train_workspace_bytes(const pcd_dgcnn_table* table, int64_t b, int64_t* bytes) {
+    PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
+    Net n;
+    int rc = table_net(table, &n);
+    if (rc != PCD_OK || (rc = check_batch(b)) != PCD_OK) return rc;
+    *bytes = tlayout(n, b, nullptr).total;
     return PCD_OK;
+}
+
+int pcd_bdgcnn_train_forward(const pcd_dgcnn_table* table, const pcd_bdgcnn_train_params* prm, const float* inputs,
+                             int64_t b, float* pooled, void* workspace, int64_t workspace_bytes, int32_t* lists_out,
+                             void* stream) {
+    Net n;
+    const int rc = table_net(table, &n);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(prm != nullptr, "params is null");
+    PCD_CHECK_ARG(prm->conv_w && prm->bn_weight && prm->bn_bias && prm->bn_mean && prm->bn_var && prm->bn_tracked &&
+                      prm->bn_eps && prm->bn_momentum, "params has a null array");
+    const ParamView v{prm->conv_w, prm->bn_weight, prm->bn_bias, prm->bn_mean, prm->bn_var, prm->bn_tracked, prm->bn_eps,
+                      prm->bn_momentum};
+    return train_forward_impl(n, v, inputs, b, pooled, workspace, workspace_bytes, lists_out, stream);
+}
+
+int pcd_bdgcnn_train_backward(const pcd_dgcnn_table* table, const float* inputs, int64_t b, const float* d_pooled,
+                              const float* pool_conv_w, void* workspace, int64_t workspace_bytes,
+                              const pcd_bdgcnn_train_grads* grads, void* stream) {
+    Net n;
+    const int rc = table_net(table, &n);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(grads != nullptr, "grads is null");
+    PCD_CHECK_ARG(grads->conv_w && grads->bn_weight && grads->bn_bias, "grads has a null array");
+    const GradView v{grads->conv_w, grads->bn_weight, grads->bn_bias};
+    return train_backward_impl(n, inputs, b, d_pooled, pool_conv_w, workspace, workspace_bytes, v, stream);
 }
 
 int pcd_dgcnn_wgrad_split(int64_t b, int64_t* patches_per_split) {
@@ -774,18 +860,24 @@ struct StageWs {
     EdgeScratch scr;
     int64_t total;
 };
-StageWs slayout(int l, int n, int64_t b, void* ws) {
+struct StageDims { int Cin, Cout; };
+StageWs slayout(StageDims d, int n, int64_t b, void* ws) {
     StageWs w{};
     Carver c{ws};
-    w.edge = carve_edge(c, l, b);
-    w.scr = carve_scratch(c, b, kCout[l], 2 * kCout[l], n, (int64_t)2 * kCout[l] * kCin[l]);
+    w.edge = carve_edge(c, d.Cin, d.Cout, b);
+    w.scr = carve_scratch(c, b, d.Cout, 2 * d.Cout, n, (int64_t)2 * d.Cout * d.Cin);
     w.total = c.used;
     return w;
 }
-int check_stage(int layer, int64_t b, int n) {
-    PCD_CHECK_ARG(layer >= 1 && layer <= 6, "layer must be in [1, 6]");
+// the arguments of a stage entry; d: edge layer `layer` (1-based) of the fixed network
+int check_stage(int layer, int64_t b, int n, StageDims* d) {
+    Net net;
+    const int rc = fixed_net(&net, 1, 1, 1);
+    if (rc != PCD_OK) return rc;
+    PCD_CHECK_ARG(layer >= 1 && layer <= net.E, "layer must be in [1, 6]");
     PCD_CHECK_ARG(b >= 1 && b <= kMaxBatch, "b must be in [1, 2^20]");
     PCD_CHECK_ARG(n >= 1 && n <= NODES, "list_len must be in [1, 64]");
+    *d = {net.Cin[layer - 1], net.Cout[layer - 1]};
     return PCD_OK;
 }
 }  // namespace
@@ -794,23 +886,23 @@ int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* be
                              float* running_mean, float* running_var, int64_t* tracked, int layer, const float* x,
                              int64_t b, const int32_t* lists, int list_len, float* out, uint8_t* argmax, double* stats,
                              void* stream) {
-    int rc = check_stage(layer, b, list_len);
+    StageDims d;
+    int rc = check_stage(layer, b, list_len, &d);
     if (rc != PCD_OK) return rc;
     PCD_CHECK_ARG(w && gamma && beta && x && lists && out && argmax && stats, "a pointer is null");
     PCD_CHECK_ARG((running_mean != nullptr) == (running_var != nullptr), "running_mean and running_var go together");
     PCD_CHECK_ARG(eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0, "eps / momentum is invalid");
-    const int l = layer - 1;
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
     char* ws;
-    PCD_HIP(tmp.alloc(&ws, slayout(l, list_len, b, nullptr).total));
-    const StageWs sw = slayout(l, list_len, b, ws);
+    PCD_HIP(tmp.alloc(&ws, slayout(d, list_len, b, nullptr).total));
+    const StageWs sw = slayout(d, list_len, b, ws);
     EdgeState s = sw.edge;
     s.arg = argmax;          // the caller's, [b][Cout][64] as the carved ones are
     s.stat = stats;
-    if ((rc = run_pack(w, l, s.Wt, s.Ws, st)) != PCD_OK) return rc;
+    if ((rc = pack_edge(w, d.Cin, d.Cout, s.Wt, s.Ws, st)) != PCD_OK) return rc;
     const BnArgs bn = bn_params(gamma, beta, running_mean, running_var, tracked, eps, momentum);
-    rc = edge_forward(edge_layer_alone(l, x, lists, list_len), s, sw.scr, bn, out, b, st);
+    rc = edge_forward(edge_layer_alone(d.Cin, d.Cout, x, lists, list_len), s, sw.scr, bn, out, b, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
@@ -819,22 +911,22 @@ int pcd_dgcnn_edgeconv_train(const float* w, const float* gamma, const float* be
 int pcd_dgcnn_edgeconv_train_backward(const float* w, const float* gamma, const float* beta, double eps, int layer,
                                       const float* x, int64_t b, const int32_t* lists, int list_len, const float* g,
                                       float* dab, float* dgamma, float* dbeta, float* dw, float* dx, void* stream) {
-    int rc = check_stage(layer, b, list_len);
+    StageDims d;
+    int rc = check_stage(layer, b, list_len, &d);
     if (rc != PCD_OK) return rc;
     PCD_CHECK_ARG(w && gamma && beta && x && lists && g && dab && dgamma && dbeta && dw, "a pointer is null");
     PCD_CHECK_ARG(eps >= 0.0, "eps is invalid");
-    const int l = layer - 1;
     hipStream_t st = as_stream(stream);
     StreamTemps tmp(st);
     char* ws;
-    PCD_HIP(tmp.alloc(&ws, slayout(l, list_len, b, nullptr).total + (int64_t)b * kCout[l] * NODES * 4));
-    const StageWs sw = slayout(l, list_len, b, ws);
+    PCD_HIP(tmp.alloc(&ws, slayout(d, list_len, b, nullptr).total + (int64_t)b * d.Cout * NODES * 4));
+    const StageWs sw = slayout(d, list_len, b, ws);
     float* out = at<float>(ws, sw.total);
-    const EdgeLayer e = edge_layer_alone(l, x, lists, list_len);
+    const EdgeLayer e = edge_layer_alone(d.Cin, d.Cout, x, lists, list_len);
     const EdgeState& s = sw.edge;
     EdgeScratch scr = sw.scr;
     scr.dP = dab;            // the caller's
-    if ((rc = run_pack(w, l, s.Wt, s.Ws, st)) != PCD_OK) return rc;
+    if ((rc = pack_edge(w, d.Cin, d.Cout, s.Wt, s.Ws, st)) != PCD_OK) return rc;
     const BnArgs bn = bn_params(gamma, beta, nullptr, nullptr, nullptr, eps, 0.0);
     // the forward again (no buffer is touched), then the backward on what it left
     if ((rc = edge_forward(e, s, scr, bn, out, b, st)) != PCD_OK) return rc;

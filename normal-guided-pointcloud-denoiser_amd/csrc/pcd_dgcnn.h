@@ -11,13 +11,37 @@ namespace pcd {
 namespace dgcnn {
 
 constexpr int NODES = 64;                                  // rows of a patch
-constexpr int kCin[6] = {17, 64, 64, 128, 256, 256};       // edge layers conv1-6
-constexpr int kCout[6] = {64, 64, 128, 256, 256, 256};
-constexpr int kCatOff[6] = {0, 64, 128, 256, 512, 768};    // the layer's slice of the [1024][64] concatenation
-constexpr int64_t kCatStride = 1024 * NODES;               // floats per patch of the concatenation
-constexpr int kHead[3] = {512, 256, 64};                   // linear1-3
 constexpr int64_t kMaxBatch = 1 << 20;   // 2^31 / (64 x 20) patches and more would pass int32 in the index flag
 constexpr int kNoBadPatch = PCD_DGCNN_NO_BAD_PATCH;
+constexpr float kTrunkSlope = 0.2f;      // LeakyReLU of every convolution; the head's is the table's
+// the bounds of a table (pcd.h states them): with them no int32 product of two widths, and no int32 grid size, overflows
+constexpr int kMaxEdge = PCD_DGCNN_MAX_EDGE_LAYERS, kMaxLin = PCD_DGCNN_MAX_LINEARS;
+constexpr int kMaxEdgeWidth = PCD_DGCNN_MAX_EDGE_WIDTH, kMaxWidth = PCD_DGCNN_MAX_WIDTH;
+
+// The layer table, on the host.  DGCNN is fixed_net(); BetterDGCNN's comes from the caller (make_net).
+struct Net {
+    int l_e = 0, l_d = 0, l_l = 0;   // static edge layers (over the index columns), dynamic ones (k-NN), linears
+    int E = 0;                       // l_e + l_d
+    int k = 0;
+    int Cin[kMaxEdge] = {}, Cout[kMaxEdge] = {};
+    int cat_off[kMaxEdge] = {};      // the layer's slice of the [Ccat][64] concatenation
+    int Ccat = 0;                    // sum of Cout
+    int Cmax = 0;                    // the widest edge layer
+    int emb = 0;                     // the pooled convolution's width
+    int head[kMaxLin] = {};          // the l_l - 1 hidden widths of the head
+    int out_ch = 0;
+    float head_slope = 0.2f;         // LeakyReLU of the head (DGCNN 0.2; BetterDGCNN F.leaky_relu's default 0.01)
+    bool fuse = false;               // eval(): narrow edge layers in one kernel where it measured faster (BetterDGCNN)
+    int64_t cat_stride() const { return (int64_t)Ccat * NODES; }   // floats per patch of the concatenation
+    int nbn() const { return E + l_l; }                            // batch norms
+    int in_of_linear(int j) const { return j == 0 ? 2 * emb : head[j - 1]; }
+    int out_of_linear(int j) const { return j < l_l - 1 ? head[j] : out_ch; }
+};
+// channel_sizes [l_e + l_d + l_l]; PCD_ERR_ARG (naming the argument) for what GCNModel.py:217-256 cannot build
+int make_net(Net* n, int l_e, int l_d, int l_l, const int* channel_sizes, int k, int init_dims, int output_channels,
+             float head_slope);
+// DGCNN(k, 17, emb, ., out_ch): 3, 3, 4, [64, 64, 128, 256, 256, 256, emb, 512, 256, 64], head slope 0.2
+int fixed_net(Net* n, int k, int emb, int output_channels);
 
 // Where edge layer l reads and writes.  g, the arg-max bytes and dL/d out are laid out as out is; dL/dX as X is.
 struct EdgeLayer {
@@ -30,24 +54,25 @@ struct EdgeLayer {
     int64_t out_off, ogs;    // the output is [b][Cout][64] at out_off floats into a buffer of patch stride ogs
 };
 
-// layer l of the network: conv1 reads inputs [b][20][64], the others the slice before theirs of cat [b][1024][64];
-// conv1-3 go over the index lists idx3 [b][64][3], conv4-6 over their third of knn [3][b][64][k]
-inline EdgeLayer edge_layer(int l, const float* inputs, const float* cat, const int32_t* idx3, int32_t* knn, int k,
+// layer l of the network: the first reads rows 0:17 of inputs [b][20][64], the others the slice before theirs of cat
+// [b][Ccat][64]; the static ones go over the index lists idx3 [b][64][3], dynamic layer d over block d of knn
+// [l_d][b][64][k]
+inline EdgeLayer edge_layer(const Net& n, int l, const float* inputs, const float* cat, const int32_t* idx3, int32_t* knn,
                             int64_t b) {
     EdgeLayer e{};
-    e.Cin = kCin[l]; e.Cout = kCout[l];
-    e.X = l == 0 ? inputs : cat + (int64_t)kCatOff[l - 1] * NODES;
-    e.xgs = l == 0 ? 20 * NODES : kCatStride;
-    e.knn = l >= 3 ? knn + (int64_t)(l - 3) * b * NODES * k : nullptr;
-    e.lists = l >= 3 ? e.knn : idx3;
-    e.kk = l >= 3 ? k : 3;
-    e.out_off = (int64_t)kCatOff[l] * NODES; e.ogs = kCatStride;
+    e.Cin = n.Cin[l]; e.Cout = n.Cout[l];
+    e.X = l == 0 ? inputs : cat + (int64_t)n.cat_off[l - 1] * NODES;
+    e.xgs = l == 0 ? 20 * NODES : n.cat_stride();
+    e.knn = l >= n.l_e ? knn + (int64_t)(l - n.l_e) * b * NODES * n.k : nullptr;
+    e.lists = l >= n.l_e ? e.knn : idx3;
+    e.kk = l >= n.l_e ? n.k : 3;
+    e.out_off = (int64_t)n.cat_off[l] * NODES; e.ogs = n.cat_stride();
     return e;
 }
-// layer l on its own (the stage entries): x [b][Cin][64] -> [b][Cout][64] over the caller's lists
-inline EdgeLayer edge_layer_alone(int l, const float* x, const int32_t* lists, int kk) {
+// a layer on its own (the stage entries): x [b][Cin][64] -> [b][Cout][64] over the caller's lists
+inline EdgeLayer edge_layer_alone(int Cin, int Cout, const float* x, const int32_t* lists, int kk) {
     EdgeLayer e{};
-    e.Cin = kCin[l]; e.Cout = kCout[l];
+    e.Cin = Cin; e.Cout = Cout;
     e.X = x; e.xgs = (int64_t)e.Cin * NODES; e.ogs = (int64_t)e.Cout * NODES;
     e.lists = lists; e.kk = kk;
     return e;
@@ -67,6 +92,7 @@ struct Carver {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // C layout of v_mfma_f32_32x32x2_f32: column = lane & 31; register r of a lane holds the tile's row (r & 3) +
 // 8 (r >> 2) + 4 (lane >> 5).  tile_row: the first row of the 32 x 32 tile, half = lane >> 5.
@@ -89,6 +115,9 @@ int index_lists(const float* inputs, int64_t b, int32_t* lists, int* flag, int p
 int index_lists_checked(const float* inputs, int64_t b, int32_t* lists, int* flag, int* bad, hipStream_t st);
 // W [M][K] -> Wt [K][M]
 int transpose(const float* W, int M, int K, float* Wt, hipStream_t st);
+// conv weight W [Cout][2 Cin] -> [W_a ; W_b - W_a] as Wt [Cin][2 Cout] and, if not null, Ws [2 Cout][Cin]
+// (csrc/dgcnn_train.hip)
+int pack_edge(const float* W, int Cin, int Cout, float* Wt, float* Ws, hipStream_t st);
 
 }  // namespace dgcnn
 }  // namespace pcd

@@ -76,6 +76,38 @@ class DgcnnTrainGrads(ctypes.Structure):
     _fields_ = [("conv_w", c_void_p * 7), ("bn_weight", c_void_p * 7), ("bn_bias", c_void_p * 7)]
 
 
+_I32P, _VPP, _F64P = POINTER(ctypes.c_int32), POINTER(c_void_p), POINTER(c_double)
+
+
+class DgcnnTableStruct(ctypes.Structure):
+    """Mirror of ``pcd_dgcnn_table`` (include/pcd.h)."""
+    _fields_ = [("l_e", ctypes.c_int32), ("l_d", ctypes.c_int32), ("l_l", ctypes.c_int32), ("channel_sizes", _I32P),
+                ("k", ctypes.c_int32), ("init_dims", ctypes.c_int32), ("output_channels", ctypes.c_int32)]
+
+
+class BdgcnnWeights(ctypes.Structure):
+    """Mirror of ``pcd_bdgcnn_weights`` (include/pcd.h)."""
+    _fields_ = [("conv_w", _VPP), ("conv_rows", _I32P), ("conv_cols", _I32P), ("bn_weight", _VPP), ("bn_bias", _VPP),
+                ("bn_mean", _VPP), ("bn_var", _VPP), ("bn_eps", _F64P), ("bn_len", _I32P), ("lin_w", _VPP),
+                ("lin_b", _VPP), ("lin_rows", _I32P), ("lin_cols", _I32P)]
+
+
+class BdgcnnDebug(ctypes.Structure):
+    """Mirror of ``pcd_bdgcnn_debug`` (include/pcd.h)."""
+    _fields_ = [("cat", c_void_p), ("lists", c_void_p), ("pooled", c_void_p), ("h", _VPP)]
+
+
+class BdgcnnTrainParams(ctypes.Structure):
+    """Mirror of ``pcd_bdgcnn_train_params`` (include/pcd.h)."""
+    _fields_ = [("conv_w", _VPP), ("bn_weight", _VPP), ("bn_bias", _VPP), ("bn_mean", _VPP), ("bn_var", _VPP),
+                ("bn_tracked", _VPP), ("bn_eps", _F64P), ("bn_momentum", _F64P)]
+
+
+class BdgcnnTrainGrads(ctypes.Structure):
+    """Mirror of ``pcd_bdgcnn_train_grads`` (include/pcd.h)."""
+    _fields_ = [("conv_w", _VPP), ("bn_weight", _VPP), ("bn_bias", _VPP)]
+
+
 # name -> (restype, argtypes); the exact export list of include/pcd.h
 _SIGS = {
     "pcd_last_error": (ctypes.c_char_p, []),
@@ -202,6 +234,21 @@ _SIGS = {
     "pcd_dgcnn_edgeconv_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64,
                                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+    "pcd_bdgcnn_create": (c_int, [POINTER(DgcnnTableStruct), POINTER(BdgcnnWeights), POINTER(c_void_p)]),
+    "pcd_bdgcnn_destroy": (c_int, [c_void_p]),
+    "pcd_bdgcnn_workspace_bytes": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "pcd_bdgcnn_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, POINTER(BdgcnnDebug),
+                                   c_void_p]),
+    "pcd_bdgcnn_forward_deferred": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                            POINTER(BdgcnnDebug), c_void_p, c_int64, c_void_p]),
+    "pcd_bdgcnn_edgeconv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int,
+                                    c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "pcd_bdgcnn_edgeconv_scratch_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_int64)]),
+    "pcd_bdgcnn_train_workspace_bytes": (c_int, [POINTER(DgcnnTableStruct), c_int64, POINTER(c_int64)]),
+    "pcd_bdgcnn_train_forward": (c_int, [POINTER(DgcnnTableStruct), POINTER(BdgcnnTrainParams), c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "pcd_bdgcnn_train_backward": (c_int, [POINTER(DgcnnTableStruct), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_int64, POINTER(BdgcnnTrainGrads), c_void_p]),
     "pcd_orient_normals_mst": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
     "pcd_orient_normals_mst_gpu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "pcd_host_eigh3": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1135,16 +1182,109 @@ host_packs = 0                       # how often Dgcnn() packed a model's weight
 DGCNN_NO_BAD_PATCH = 0x7f7f7f7f      # PCD_DGCNN_NO_BAD_PATCH
 
 
+class DgcnnTable:
+    """The layer table of a network (pcd_dgcnn_table): l_e static edge convolutions, l_d dynamic ones, l_l linears,
+    the l_e + l_d + l_l channel sizes, k, init_dims, output_channels -- BetterDGCNN's constructor arguments
+    (GCNModel.py:217-256).  Refuses, naming the argument, what the reference cannot build or the kernels do not index
+    (the bounds of include/pcd.h).  `fixed(k, emb_dims, output_channels)` is DGCNN's table."""
+    MAX_EDGE_LAYERS, MAX_LINEARS, MAX_EDGE_WIDTH, MAX_WIDTH = 16, 16, 4096, 65536
+
+    def __init__(self, l_e, l_d, l_l, channel_sizes, k, init_dims=17, output_channels=3, what="BetterDGCNN"):
+        if isinstance(channel_sizes, torch.Tensor):
+            if channel_sizes.dim() != 1 or channel_sizes.dtype.is_floating_point or channel_sizes.dtype == torch.bool:
+                raise ValueError(f"{what}: channel_sizes must be a 1-D integer tensor or a sequence of ints")
+            sizes = [int(v) for v in channel_sizes.tolist()]
+        else:
+            sizes = list(channel_sizes)
+            if any(int(v) != v for v in sizes):
+                raise ValueError(f"{what}: channel_sizes must hold integers, got {sizes}")
+            sizes = [int(v) for v in sizes]
+        for name, v in (("l_e", l_e), ("l_d", l_d), ("l_l", l_l), ("k", k), ("init_dims", init_dims),
+                        ("output_channels", output_channels)):
+            if int(v) != v:
+                raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
+        l_e, l_d, l_l = int(l_e), int(l_d), int(l_l)
+        if l_e < 0 or l_d < 0 or not 1 <= l_e + l_d <= self.MAX_EDGE_LAYERS:
+            raise ValueError(f"{what}: l_e + l_d must be in [1, {self.MAX_EDGE_LAYERS}] (without an edge layer there is "
+                             f"nothing to concatenate), got l_e = {l_e}, l_d = {l_d}")
+        if not 2 <= l_l <= self.MAX_LINEARS:
+            raise ValueError(f"{what}: l_l must be in [2, {self.MAX_LINEARS}] (the last linear reads channel_sizes[-1], "
+                             f"a hidden width), got {l_l}")
+        if len(sizes) != l_e + l_d + l_l:
+            raise ValueError(f"{what}: channel_sizes must have l_e + l_d + l_l = {l_e + l_d + l_l} entries, got {len(sizes)}")
+        for i, v in enumerate(sizes):
+            lim = self.MAX_EDGE_WIDTH if i < l_e + l_d else self.MAX_WIDTH
+            if not 1 <= v <= lim:
+                raise ValueError(f"{what}: channel_sizes[{i}] must be in [1, {lim}], got {v}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError(f"{what}: k must be in [1, 64], got {k}")
+        if int(init_dims) != 17:
+            raise ValueError(f"{what}: init_dims must be 17 (forward takes rows 0:17 of its input), got {init_dims}")
+        if not 1 <= int(output_channels) <= 4096:
+            raise ValueError(f"{what}: output_channels must be in [1, 4096], got {output_channels}")
+        self.l_e, self.l_d, self.l_l, self.sizes = l_e, l_d, l_l, tuple(sizes)
+        self.k, self.init_dims, self.output_channels = int(k), int(init_dims), int(output_channels)
+        E = self.n_edge = l_e + l_d
+        self.cin = (17,) + self.sizes[:E - 1]          # (in, out) of the edge convolutions
+        self.cout = self.sizes[:E]
+        self.cat_off = tuple(sum(self.cout[:i]) for i in range(E + 1))
+        self.ccat = self.cat_off[-1]
+        self.emb = self.sizes[E]                        # the pooled convolution's width
+        self.head = self.sizes[E + 1:]                  # the l_l - 1 hidden widths
+        self._sizes_c = (ctypes.c_int32 * len(sizes))(*sizes)
+        self.struct = DgcnnTableStruct(l_e, l_d, l_l, ctypes.cast(self._sizes_c, _I32P), self.k, self.init_dims,
+                                       self.output_channels)
+
+    @classmethod
+    def fixed(cls, k, emb_dims, output_channels=3):
+        if int(emb_dims) != emb_dims or not 1 <= int(emb_dims) <= cls.MAX_WIDTH:
+            raise ValueError(f"DGCNN: emb_dims must be an integer in [1, {cls.MAX_WIDTH}], got {emb_dims!r}")
+        return cls(3, 3, 4, DGCNN_COUT + (int(emb_dims), 512, 256, 64), k, 17, output_channels, what="DGCNN")
+
+    def conv_shapes(self):
+        """[rows, cols] of the l_e + l_d + 1 convolution weights."""
+        return [(co, 2 * ci) for ci, co in zip(self.cin, self.cout)] + [(self.emb, self.ccat)]
+
+    def list_len(self, layer):
+        """The neighbour list length of edge layer `layer` (0-based)."""
+        return 3 if layer < self.l_e else self.k
+
+    def byref(self):
+        return ctypes.byref(self.struct)
+
+
+def _voidp_array(values):
+    return (c_void_p * len(values))(*values)
+
+
 class Dgcnn:
     """Packed device weights of one DGCNN (pcd_dgcnn) and its forward.
 
     conv: 7 weights [out, 2 in] (conv7 [emb, 1024]); bn: 10 tuples (weight, bias, running_mean, running_var, eps);
     lin: 4 tuples (weight [out, in], bias or None).  The tensors may live on the host or the device (float32); they
     are copied."""
+    _NAME = "DGCNN"
 
     def __init__(self, conv, bn, lin, k, init_dims, emb_dims, output_channels=3):
         if len(conv) != 7 or len(bn) != 10 or len(lin) != 4:
             raise ValueError("pcd: Dgcnn takes 7 convolution weights, 10 batch norms and 4 linears")
+        w = DgcnnWeights()
+        keep = self._fill(w, conv, bn, lin)
+        global host_packs
+        host_packs += 1
+        h = c_void_p()
+        device()
+        check(lib().pcd_dgcnn_create(ctypes.byref(w), int(k), int(init_dims), int(emb_dims), int(output_channels),
+                                     ctypes.byref(h)), "pcd_dgcnn_create")
+        del keep
+        self.handle = h
+        self.k, self.emb_dims, self.output_channels = int(k), int(emb_dims), int(output_channels)
+        self.table = DgcnnTable.fixed(k, emb_dims, output_channels)
+
+    @staticmethod
+    def _fill(w, conv, bn, lin):
+        """Writes the pointers and shapes of the weights into the (array or pointer) fields of `w`; returns what must
+        stay alive until the library has copied them."""
         keep = []
 
         def p32(t):
@@ -1154,7 +1294,6 @@ class Dgcnn:
             keep.append(t)
             return t.data_ptr()
 
-        w = DgcnnWeights()
         for i, cw in enumerate(conv):
             cw2 = cw.reshape(cw.shape[0], -1)
             w.conv_w[i], w.conv_rows[i], w.conv_cols[i] = p32(cw2), cw2.shape[0], cw2.shape[1]
@@ -1168,14 +1307,7 @@ class Dgcnn:
                 raise ValueError(f"pcd: linear{i + 1}: weight must be [out, in] and the bias [out]")
             w.lin_w[i], w.lin_rows[i], w.lin_cols[i] = p32(lw), lw.shape[0], lw.shape[1]
             w.lin_b[i] = None if lb is None else p32(lb)
-        global host_packs
-        host_packs += 1
-        h = c_void_p()
-        device()
-        check(lib().pcd_dgcnn_create(ctypes.byref(w), int(k), int(init_dims), int(emb_dims), int(output_channels),
-                                     ctypes.byref(h)), "pcd_dgcnn_create")
-        self.handle = h
-        self.k, self.emb_dims, self.output_channels = int(k), int(emb_dims), int(output_channels)
+        return keep
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -1191,6 +1323,24 @@ class Dgcnn:
     def workspace(self, b: int) -> torch.Tensor:
         return torch.empty(max(self.workspace_bytes(b), 1), dtype=torch.uint8, device=device())
 
+    def _debug_tensors(self, b, dev):
+        t = self.table
+        d = {"cat": torch.empty((b, t.ccat, 64), dtype=torch.float32, device=dev),
+             "lists": torch.empty((t.l_d, b, 64, t.k), dtype=torch.int32, device=dev),
+             "pooled": torch.empty((b, 2 * t.emb), dtype=torch.float32, device=dev)}
+        for j, width in enumerate(t.head, start=1):
+            d[f"h{j}"] = torch.empty((width, b), dtype=torch.float32, device=dev)
+        return d
+
+    def _debug(self, b, dev):
+        """(the tensors the debug struct fills, the struct, what the struct points to)"""
+        d = self._debug_tensors(b, dev)
+        return d, DgcnnDebug(*[d[n].data_ptr() for n in ("cat", "lists", "pooled", "h1", "h2", "h3")]), None
+
+    def _forward_entries(self):
+        return (lib().pcd_dgcnn_forward, "pcd_dgcnn_forward", lib().pcd_dgcnn_forward_deferred,
+                "pcd_dgcnn_forward_deferred")
+
     def forward(self, inputs: torch.Tensor, workspace: torch.Tensor = None, debug: bool = False,
                 first_bad: torch.Tensor = None, patch_base: int = 0):
         """inputs [b, 20, 64] float32 on the device -> out [b, output_channels]; with debug also a dict of the
@@ -1200,48 +1350,118 @@ class Dgcnn:
         tensor takes the lowest patch_base + patch with a bad index column (pcd_dgcnn_forward_deferred)."""
         x = f32(inputs)
         if x.dim() != 3 or x.size(1) != 20 or x.size(2) != 64:
-            raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
+            raise ValueError(f"pcd: {self._NAME} inputs must be [b, 20, 64], got {tuple(inputs.shape)}")
         b, dev = x.size(0), x.device
         ws = self.workspace(b) if workspace is None else workspace
         if not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous():
-            raise ValueError(f"pcd: DGCNN workspace must be a contiguous tensor on {dev}, got "
+            raise ValueError(f"pcd: {self._NAME} workspace must be a contiguous tensor on {dev}, got "
                              f"{getattr(ws, 'device', type(ws).__name__)}")
         if first_bad is not None and (not isinstance(first_bad, torch.Tensor) or first_bad.device != dev
                                       or first_bad.dtype != torch.int32 or first_bad.numel() != 1):
-            raise ValueError(f"pcd: DGCNN first_bad must be an int32 tensor of one element on {dev}")
+            raise ValueError(f"pcd: {self._NAME} first_bad must be an int32 tensor of one element on {dev}")
         out = torch.empty((b, self.output_channels), dtype=torch.float32, device=dev)
-        dbg, d = None, None
+        dbg, d, held = None, None, None
         if debug:
-            d = {"cat": torch.empty((b, 1024, 64), dtype=torch.float32, device=dev),
-                 "lists": torch.empty((3, b, 64, self.k), dtype=torch.int32, device=dev),
-                 "pooled": torch.empty((b, 2 * self.emb_dims), dtype=torch.float32, device=dev),
-                 "h1": torch.empty((512, b), dtype=torch.float32, device=dev),
-                 "h2": torch.empty((256, b), dtype=torch.float32, device=dev),
-                 "h3": torch.empty((64, b), dtype=torch.float32, device=dev)}
-            dbg = DgcnnDebug(*[d[n].data_ptr() for n in ("cat", "lists", "pooled", "h1", "h2", "h3")])
+            d, dbg, held = self._debug(b, dev)
         dbg_ref = None if dbg is None else ctypes.byref(dbg)
+        fwd, fwd_name, deferred, deferred_name = self._forward_entries()
         if first_bad is None:
-            check(lib().pcd_dgcnn_forward(self.handle, ptr(x), b, ptr(out), ptr(ws), ws.numel() * ws.element_size(),
-                                          dbg_ref, c_void_p(stream_ptr())), "pcd_dgcnn_forward")
+            check(fwd(self.handle, ptr(x), b, ptr(out), ptr(ws), ws.numel() * ws.element_size(), dbg_ref,
+                      c_void_p(stream_ptr())), fwd_name)
         else:
-            check(lib().pcd_dgcnn_forward_deferred(self.handle, ptr(x), b, ptr(out), ptr(ws),
-                                                   ws.numel() * ws.element_size(), dbg_ref, ptr(first_bad),
-                                                   int(patch_base), c_void_p(stream_ptr())),
-                  "pcd_dgcnn_forward_deferred")
+            check(deferred(self.handle, ptr(x), b, ptr(out), ptr(ws), ws.numel() * ws.element_size(), dbg_ref,
+                           ptr(first_bad), int(patch_base), c_void_p(stream_ptr())), deferred_name)
+        del held
         return (out, d) if debug else out
 
     def edgeconv(self, layer: int, x: torch.Tensor, lists: torch.Tensor) -> torch.Tensor:
-        """Layer 1-6 on x [b, Cin, 64] with neighbour lists int32 [b, 64, n] -> [b, Cout, 64] (pcd_dgcnn_edgeconv)."""
-        if not 1 <= int(layer) <= 6:
-            raise ValueError("pcd: DGCNN edge layers are 1-6")
+        """Edge layer `layer` (1-based) on x [b, Cin, 64] with neighbour lists int32 [b, 64, n] -> [b, Cout, 64]
+        (pcd_dgcnn_edgeconv)."""
+        t = self.table
+        if not 1 <= int(layer) <= t.n_edge:
+            raise ValueError(f"pcd: {self._NAME} edge layers are 1-{t.n_edge}")
         x, lists = f32(x), on_device(lists, torch.int32)
         b = x.size(0)
-        if tuple(x.shape) != (b, DGCNN_CIN[layer - 1], 64) or lists.dim() != 3 or tuple(lists.shape[:2]) != (b, 64):
+        if tuple(x.shape) != (b, t.cin[layer - 1], 64) or lists.dim() != 3 or tuple(lists.shape[:2]) != (b, 64):
             raise ValueError(f"pcd: edgeconv layer {layer}: x {tuple(x.shape)} / lists {tuple(lists.shape)} do not fit")
-        out = torch.empty((b, DGCNN_COUT[layer - 1], 64), dtype=torch.float32, device=x.device)
+        out = torch.empty((b, t.cout[layer - 1], 64), dtype=torch.float32, device=x.device)
         check(lib().pcd_dgcnn_edgeconv(self.handle, int(layer), ptr(x), b, ptr(lists), lists.size(2), ptr(out),
                                        c_void_p(stream_ptr())), "pcd_dgcnn_edgeconv")
         return out
+
+
+class BetterDgcnn(Dgcnn):
+    """Packed device weights of one BetterDGCNN (pcd_bdgcnn_create) and its forward: Dgcnn with the layer table from
+    the caller.  table: a DgcnnTable; conv: l_e + l_d + 1 weights; bn: l_e + l_d + l_l tuples; lin: l_l tuples."""
+    _NAME = "BetterDGCNN"
+
+    def __init__(self, table: DgcnnTable, conv, bn, lin):
+        if len(conv) != table.n_edge + 1 or len(bn) != table.n_edge + table.l_l or len(lin) != table.l_l:
+            raise ValueError(f"pcd: BetterDgcnn takes {table.n_edge + 1} convolution weights, "
+                             f"{table.n_edge + table.l_l} batch norms and {table.l_l} linears")
+        w, arrays = BdgcnnWeights(), []
+        for name, typ in BdgcnnWeights._fields_:        # the pointer fields' arrays, of the table's lengths
+            n = len(conv) if name.startswith("conv") else len(bn) if name.startswith("bn") else len(lin)
+            arrays.append((typ._type_ * n)())
+            setattr(w, name, ctypes.cast(arrays[-1], typ))
+        keep = self._fill(w, conv, bn, lin) + arrays
+        global host_packs
+        host_packs += 1
+        h = c_void_p()
+        device()
+        check(lib().pcd_bdgcnn_create(table.byref(), ctypes.byref(w), ctypes.byref(h)), "pcd_bdgcnn_create")
+        del keep
+        self.handle = h
+        self.table = table
+        self.k, self.emb_dims, self.output_channels = table.k, table.emb, table.output_channels
+
+    def _debug(self, b, dev):
+        d = self._debug_tensors(b, dev)
+        hs = _voidp_array([d[f"h{j}"].data_ptr() for j in range(1, len(self.table.head) + 1)])
+        return d, BdgcnnDebug(d["cat"].data_ptr(), d["lists"].data_ptr(), d["pooled"].data_ptr(),
+                              ctypes.cast(hs, _VPP)), hs
+
+    def _forward_entries(self):
+        return (lib().pcd_bdgcnn_forward, "pcd_bdgcnn_forward", lib().pcd_bdgcnn_forward_deferred,
+                "pcd_bdgcnn_forward_deferred")
+
+
+FUSED_OFF, FUSED_ON, FUSED_AUTO = range(3)       # PCD_FUSED_*
+
+
+def bdgcnn_edgeconv_scratch_bytes(c_in: int, c_out: int, b: int) -> int:
+    v = c_int64(0)
+    check(lib().pcd_bdgcnn_edgeconv_scratch_bytes(int(c_in), int(c_out), int(b), ctypes.byref(v)),
+          "pcd_bdgcnn_edgeconv_scratch_bytes")
+    return v.value
+
+
+def bdgcnn_edgeconv(w, s, t, x, lists, fused: int = FUSED_AUTO, scratch=None, out=None):
+    """One edge layer in eval() by its shapes (pcd_bdgcnn_edgeconv): w [Cout, 2 Cin], the folded batch norm s, t
+    [Cout], x [b, Cin, 64], lists int32 [b, 64, n] -> [b, Cout, 64].  fused: FUSED_OFF (GEMM, then the max over the
+    lists), FUSED_ON (one kernel, 2 Cout <= 128 only) or FUSED_AUTO (the library's choice); the bits are the same.
+    scratch: None, or a contiguous device tensor of bdgcnn_edgeconv_scratch_bytes(Cin, Cout, b) bytes -- then nothing
+    is allocated and nothing waits for the device; out: None or the float32 [b, Cout, 64] tensor to write."""
+    w, s, t, x, lists = f32(w), f32(s), f32(t), f32(x), on_device(lists, torch.int32)
+    w = w.reshape(w.shape[0], -1)
+    b, cout = x.size(0), w.size(0)
+    if x.dim() != 3 or x.size(2) != 64 or w.size(1) != 2 * x.size(1) or s.numel() != cout or t.numel() != cout \
+            or lists.dim() != 3 or tuple(lists.shape[:2]) != (b, 64):
+        raise ValueError(f"pcd: bdgcnn_edgeconv: w {tuple(w.shape)} / x {tuple(x.shape)} / lists {tuple(lists.shape)} "
+                         "do not fit")
+    if scratch is not None and (not isinstance(scratch, torch.Tensor) or scratch.device != x.device
+                                or not scratch.is_contiguous()):
+        raise ValueError(f"pcd: bdgcnn_edgeconv: scratch must be a contiguous tensor on {x.device}")
+    if out is None:
+        out = torch.empty((b, cout, 64), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (b, cout, 64) or out.device != x.device \
+            or not out.is_contiguous():
+        raise ValueError(f"pcd: bdgcnn_edgeconv: out must be float32 [{b}, {cout}, 64] contiguous on {x.device}")
+    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
+    check(lib().pcd_bdgcnn_edgeconv(ptr(w), ptr(s), ptr(t), x.size(1), cout, ptr(x), b, ptr(lists), lists.size(2),
+                                    int(fused), ptr(out), ptr(scratch), nbytes, c_void_p(stream_ptr())),
+          "pcd_bdgcnn_edgeconv")
+    return out
 
 
 def dgcnn_knn(x: torch.Tensor, k: int) -> torch.Tensor:
@@ -1307,6 +1527,51 @@ def _train_workspace(ws, dev):
     return ws.numel() * ws.element_size()
 
 
+def _train_params(table, conv, bn, inputs):
+    """The checks of a train-mode forward; -> (b, device, the eight per-layer lists of pcd_*_train_params)."""
+    n = table.n_edge + 1
+    if len(conv) != n or len(bn) != n:
+        raise ValueError(f"pcd: DGCNN training takes {n} convolution weights and {n} batch norms")
+    x = inputs
+    _train_tensor(x, "inputs")
+    if x.dim() != 3 or x.size(1) != 20 or x.size(2) != 64:
+        raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(x.shape)}")
+    cols = {key: [] for key in ("conv_w", "bn_weight", "bn_bias", "bn_mean", "bn_var", "bn_tracked", "bn_eps",
+                                "bn_momentum")}
+    shapes = table.conv_shapes()
+    for i, cw in enumerate(conv):
+        rows, width = shapes[i]
+        if cw.numel() != rows * width or cw.shape[0] != rows:
+            raise ValueError(f"pcd: conv{i + 1} weight must be [{rows}, {width}], got {tuple(cw.shape)}")
+        cols["conv_w"].append(_train_tensor(cw, f"conv{i + 1} weight"))
+    for i, (g, be, mu, var, nbt, eps, mom) in enumerate(bn):
+        if mom is None:
+            raise ValueError(f"pcd: bn{i + 1}: momentum=None (a cumulative average) is not supported in training")
+        for t, what in ((g, "weight"), (be, "bias"), (mu, "running_mean"), (var, "running_var")):
+            if t is not None and t.numel() != shapes[i][0]:
+                raise ValueError(f"pcd: bn{i + 1}.{what} must have {shapes[i][0]} channels")
+        cols["bn_weight"].append(_train_tensor(g, f"bn{i + 1}.weight"))
+        cols["bn_bias"].append(_train_tensor(be, f"bn{i + 1}.bias"))
+        cols["bn_mean"].append(None if mu is None else _train_tensor(mu, f"bn{i + 1}.running_mean"))
+        cols["bn_var"].append(None if var is None else _train_tensor(var, f"bn{i + 1}.running_var"))
+        cols["bn_tracked"].append(None if nbt is None else
+                                  _train_tensor(nbt, f"bn{i + 1}.num_batches_tracked", torch.int64))
+        cols["bn_eps"].append(float(eps))
+        cols["bn_momentum"].append(float(mom))
+    return x.size(0), x.device, cols
+
+
+def _pointer_struct(struct, cols):
+    """A struct of pointer fields over arrays made from `cols` {field: list}; -> (struct, the arrays to keep alive)."""
+    keep = []
+    for name, values in cols.items():
+        typ = c_double if name in ("bn_eps", "bn_momentum") else c_void_p
+        arr = (typ * len(values))(*values)
+        keep.append(arr)
+        setattr(struct, name, ctypes.cast(arr, POINTER(typ)))
+    return struct, keep
+
+
 def dgcnn_train_forward(conv, bn, k: int, emb_dims: int, inputs: torch.Tensor, workspace: torch.Tensor,
                         want_lists: bool = False):
     """conv1-7 and the pooling in train() (pcd_dgcnn_train_forward).  conv: 7 weights [out, 2 in(, 1, 1)]; bn: 7 tuples
@@ -1316,56 +1581,84 @@ def dgcnn_train_forward(conv, bn, k: int, emb_dims: int, inputs: torch.Tensor, w
     workspace (dgcnn_train_workspace_bytes) carries the forward's state to dgcnn_train_backward."""
     if len(conv) != 7 or len(bn) != 7:
         raise ValueError("pcd: DGCNN training takes 7 convolution weights and 7 batch norms")
-    x = inputs
-    _train_tensor(x, "inputs")
-    if x.dim() != 3 or x.size(1) != 20 or x.size(2) != 64:
-        raise ValueError(f"pcd: DGCNN inputs must be [b, 20, 64], got {tuple(x.shape)}")
-    b, dev = x.size(0), x.device
+    b, dev, cols = _train_params(DgcnnTable.fixed(k, emb_dims), conv, bn, inputs)
     prm = DgcnnTrainParams()
-    rows = list(DGCNN_COUT) + [int(emb_dims)]
-    cols = [2 * c for c in DGCNN_CIN] + [1024]
-    for i, cw in enumerate(conv):
-        if cw.numel() != rows[i] * cols[i] or cw.shape[0] != rows[i]:
-            raise ValueError(f"pcd: conv{i + 1} weight must be [{rows[i]}, {cols[i]}], got {tuple(cw.shape)}")
-        prm.conv_w[i] = _train_tensor(cw, f"conv{i + 1} weight")
-    for i, (g, be, mu, var, nbt, eps, mom) in enumerate(bn):
-        if mom is None:
-            raise ValueError(f"pcd: bn{i + 1}: momentum=None (a cumulative average) is not supported in training")
-        for t, what in ((g, "weight"), (be, "bias"), (mu, "running_mean"), (var, "running_var")):
-            if t is not None and t.numel() != rows[i]:
-                raise ValueError(f"pcd: bn{i + 1}.{what} must have {rows[i]} channels")
-        prm.bn_weight[i], prm.bn_bias[i] = _train_tensor(g, f"bn{i + 1}.weight"), _train_tensor(be, f"bn{i + 1}.bias")
-        prm.bn_mean[i] = None if mu is None else _train_tensor(mu, f"bn{i + 1}.running_mean")
-        prm.bn_var[i] = None if var is None else _train_tensor(var, f"bn{i + 1}.running_var")
-        prm.bn_tracked[i] = None if nbt is None else _train_tensor(nbt, f"bn{i + 1}.num_batches_tracked", torch.int64)
-        prm.bn_eps[i], prm.bn_momentum[i] = float(eps), float(mom)
+    for name, values in cols.items():
+        for i, v in enumerate(values):
+            getattr(prm, name)[i] = v
     nbytes = _train_workspace(workspace, dev)
     pooled = torch.empty((b, 2 * int(emb_dims)), dtype=torch.float32, device=dev)
     lists = torch.empty((3, b, 64, int(k)), dtype=torch.int32, device=dev) if want_lists else None
-    check(lib().pcd_dgcnn_train_forward(ctypes.byref(prm), int(k), int(emb_dims), ptr(x), b, ptr(pooled), ptr(workspace),
-                                        nbytes, ptr(lists), c_void_p(stream_ptr())), "pcd_dgcnn_train_forward")
+    check(lib().pcd_dgcnn_train_forward(ctypes.byref(prm), int(k), int(emb_dims), ptr(inputs), b, ptr(pooled),
+                                        ptr(workspace), nbytes, ptr(lists), c_void_p(stream_ptr())),
+          "pcd_dgcnn_train_forward")
     return (pooled, lists) if want_lists else pooled
+
+
+def _train_grads(conv, inputs, d_pooled, emb):
+    x = inputs
+    _train_tensor(x, "inputs")
+    b, dev = x.size(0), x.device
+    dp = f32(d_pooled)
+    if tuple(dp.shape) != (b, 2 * int(emb)):
+        raise ValueError(f"pcd: d_pooled must be [{b}, {2 * int(emb)}], got {tuple(dp.shape)}")
+    dw = [torch.empty_like(cw, memory_format=torch.contiguous_format) for cw in conv]
+    dg = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
+    db = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
+    return b, dev, dp, dw, dg, db
 
 
 def dgcnn_train_backward(conv, k: int, emb_dims: int, inputs: torch.Tensor, d_pooled: torch.Tensor,
                          workspace: torch.Tensor):
     """d_pooled [b, 2 emb] -> (7 conv weight gradients shaped like conv, 7 bn weight gradients, 7 bn bias gradients)
     from the workspace dgcnn_train_forward left (pcd_dgcnn_train_backward).  One backward per forward."""
-    x = inputs
-    _train_tensor(x, "inputs")
-    b, dev = x.size(0), x.device
-    dp = f32(d_pooled)
-    if tuple(dp.shape) != (b, 2 * int(emb_dims)):
-        raise ValueError(f"pcd: d_pooled must be [{b}, {2 * int(emb_dims)}], got {tuple(dp.shape)}")
+    b, dev, dp, dw, dg, db = _train_grads(conv, inputs, d_pooled, emb_dims)
     g = DgcnnTrainGrads()
-    dw = [torch.empty_like(cw, memory_format=torch.contiguous_format) for cw in conv]
-    dg = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
-    db = [torch.empty(cw.shape[0], dtype=torch.float32, device=dev) for cw in conv]
     for i in range(7):
         g.conv_w[i], g.bn_weight[i], g.bn_bias[i] = dw[i].data_ptr(), dg[i].data_ptr(), db[i].data_ptr()
-    check(lib().pcd_dgcnn_train_backward(int(k), int(emb_dims), ptr(x), b, ptr(dp), c_void_p(_train_tensor(conv[6], "conv7 weight")),
+    check(lib().pcd_dgcnn_train_backward(int(k), int(emb_dims), ptr(inputs), b, ptr(dp),
+                                         c_void_p(_train_tensor(conv[6], "conv7 weight")),
                                          ptr(workspace), _train_workspace(workspace, dev), ctypes.byref(g),
                                          c_void_p(stream_ptr())), "pcd_dgcnn_train_backward")
+    return dw, dg, db
+
+
+def bdgcnn_train_workspace_bytes(table: DgcnnTable, b: int) -> int:
+    v = c_int64(0)
+    check(lib().pcd_bdgcnn_train_workspace_bytes(table.byref(), int(b), ctypes.byref(v)),
+          "pcd_bdgcnn_train_workspace_bytes")
+    return v.value
+
+
+def bdgcnn_train_forward(table: DgcnnTable, conv, bn, inputs: torch.Tensor, workspace: torch.Tensor,
+                         want_lists: bool = False):
+    """dgcnn_train_forward for a table from the caller (pcd_bdgcnn_train_forward): conv and bn hold l_e + l_d + 1
+    entries; -> pooled [b, 2 C]; with want_lists also the dynamic layers' lists, int32 [l_d, b, 64, k]."""
+    b, dev, cols = _train_params(table, conv, bn, inputs)
+    prm, keep = _pointer_struct(BdgcnnTrainParams(), cols)
+    nbytes = _train_workspace(workspace, dev)
+    pooled = torch.empty((b, 2 * table.emb), dtype=torch.float32, device=dev)
+    lists = torch.empty((table.l_d, b, 64, table.k), dtype=torch.int32, device=dev) if want_lists else None
+    check(lib().pcd_bdgcnn_train_forward(table.byref(), ctypes.byref(prm), ptr(inputs), b, ptr(pooled), ptr(workspace),
+                                         nbytes, ptr(lists), c_void_p(stream_ptr())), "pcd_bdgcnn_train_forward")
+    del keep
+    return (pooled, lists) if want_lists else pooled
+
+
+def bdgcnn_train_backward(table: DgcnnTable, conv, inputs: torch.Tensor, d_pooled: torch.Tensor,
+                          workspace: torch.Tensor):
+    """dgcnn_train_backward for a table from the caller (pcd_bdgcnn_train_backward)."""
+    if len(conv) != table.n_edge + 1:
+        raise ValueError(f"pcd: DGCNN training takes {table.n_edge + 1} convolution weights")
+    b, dev, dp, dw, dg, db = _train_grads(conv, inputs, d_pooled, table.emb)
+    g, keep = _pointer_struct(BdgcnnTrainGrads(), {"conv_w": [t.data_ptr() for t in dw],
+                                                   "bn_weight": [t.data_ptr() for t in dg],
+                                                   "bn_bias": [t.data_ptr() for t in db]})
+    check(lib().pcd_bdgcnn_train_backward(table.byref(), ptr(inputs), b, ptr(dp),
+                                          c_void_p(_train_tensor(conv[-1], "the pooled convolution's weight")),
+                                          ptr(workspace), _train_workspace(workspace, dev), ctypes.byref(g),
+                                          c_void_p(stream_ptr())), "pcd_bdgcnn_train_backward")
+    del keep
     return dw, dg, db
 
 
