@@ -38,6 +38,8 @@
  *   pcd_bdgcnn_forward(_deferred)   BetterDGCNN.forward (eval)                 PatchGeneration/Modules/Network/GCNModel.py:258-297
  *   pcd_bdgcnn_edgeconv(_scratch_bytes)
  *                                   one edge layer of it: convN + max          PatchGeneration/Modules/Network/GCNModel.py:270-281
+ *   pcd_dgcnn_set_operands / _operands / _gemm_bf16, pcd_bdgcnn_edgeconv_bf16
+ *                                   the opt-in bf16-operand inference mode of both networks (no counterpart)
  *   pcd_bdgcnn_train_workspace_bytes / _train_forward / _train_backward
  *                                   BetterDGCNN.forward (train) up to the pooling, and loss.backward() below it
  *                                                                              PatchGeneration/Modules/Network/GCNModel.py:258-287
@@ -647,7 +649,34 @@ int pcd_bdgcnn_forward_deferred(const pcd_dgcnn* m, const float* inputs, int64_t
 int pcd_bdgcnn_edgeconv(const float* w, const float* s, const float* t, int c_in, int c_out, const float* x, int64_t b,
                         const int32_t* lists, int list_len, int fused, float* out, void* scratch, int64_t scratch_bytes,
                         void* stream);
+/* The size serves pcd_bdgcnn_edgeconv and pcd_bdgcnn_edgeconv_bf16 alike (the bf16 weight lies where the packed
+ * float32 weight would; its rows are padded to 8 k, which shows in the size only for c_in < 7). */
 int pcd_bdgcnn_edgeconv_scratch_bytes(int c_in, int c_out, int64_t b, int64_t* bytes);
+
+/* ------------------------------------------------------------------ bf16 operands (opt-in, inference only) */
+/* With PCD_OPERANDS_BF16 the trunk's GEMMs -- every edge layer with Cin >= 32 and the pooled convolution -- run on
+ * v_mfma_f32_32x32x16_bf16: the activations (float32 in memory, as before: workspace sizes do not change) and the
+ * packed float32 weights [W_a ; W_b - W_a], W7 are rounded to bf16 (nearest even; NaN and Inf kept) and the products
+ * are accumulated in float32.  The folded batch norms, LeakyReLU, max over the lists and the pooling stay float32,
+ * in the order of the float32 mode; edge layers with Cin < 32 (the first) and the head stay on the float32 kernel.
+ * A patch's output still depends on that patch alone: the same bits in any batch, at any place in it, in every run.
+ * What is lost is precision: the outputs differ from the float32 mode's at the 1e-2 level.
+ * set_operands serves handles of either create entry; the first switch to bf16 allocates and rounds the weights
+ * (synchronous); switching back uses the float32 weights again, bit for bit.  PCD_ERR_ARG for any other value.
+ * pcd_dgcnn_forward(_deferred), pcd_bdgcnn_forward(_deferred) and pcd_dgcnn_edgeconv follow the handle's setting; the
+ * training entries take no handle and are float32. */
+#define PCD_OPERANDS_F32 0
+#define PCD_OPERANDS_BF16 1
+int pcd_dgcnn_set_operands(pcd_dgcnn* m, int operands);
+int pcd_dgcnn_operands(const pcd_dgcnn* m, int* operands);
+/* Stages, for tests.  gemm_bf16: pcd_dgcnn_gemm with nodes = 64 on the bf16 kernel -- float32 w [M][K] and
+ * x [b][K][64] are rounded as the forward rounds them; epilogues 0-3; any K >= 1 (no Cin < 32 exception).
+ * edgeconv_bf16: pcd_bdgcnn_edgeconv on the bf16 kernel, whatever c_in is; fused ON = OFF bit for bit. */
+int pcd_dgcnn_gemm_bf16(const float* w, const float* x, int m_rows, int k_cols, int64_t b, int epilogue, const float* s,
+                        const float* t, float* y, void* stream);
+int pcd_bdgcnn_edgeconv_bf16(const float* w, const float* s, const float* t, int c_in, int c_out, const float* x,
+                             int64_t b, const int32_t* lists, int list_len, int fused, float* out, void* scratch,
+                             int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------ DGCNN training (train(), fp32) */
 /* conv1-7 and the max / mean pooling of DGCNN.forward with self.training (GCNModel.py:170-207): batch norms take the

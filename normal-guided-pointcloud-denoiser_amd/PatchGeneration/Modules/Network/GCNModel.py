@@ -25,6 +25,12 @@ through its torch submodules -- in BetterDGCNN the batch norms on float64 views 
 Gradients reach every parameter; there is none with respect to the inputs, and the neighbour lists are constants of the
 backward.  The reference's data loaders are not part of this package; saveModel /
 loadModel and the training loop are in PatchGeneration/Modules/NetworkController.py.
+
+`operands="bf16"` (constructor keyword, or `model.set_operands("bf16")`; the default is "fp32") is an opt-in inference
+mode: the convolutions' GEMMs -- every edge layer with at least 32 input channels and the pooled convolution -- take
+their operands rounded to bf16 and accumulate in float32 (include/pcd.h, "bf16 operands").  Faster and less precise;
+a patch's output still depends on that patch alone, bit for bit.  The setting is no part of the state dict, survives
+load_state_dict / .to / in-place writes, and train() ignores it.
 """
 from __future__ import annotations
 
@@ -97,7 +103,9 @@ class _TableNet(nn.Module):
     _HEAD_SLOPE = 0.2
     _HEAD_BN_WIDE = False            # train(): the head's batch norms on float64 views (_batch_norm_wide)
 
-    def _build(self, table, dropout, trainable):
+    def _build(self, table, dropout, trainable, operands="fp32"):
+        _nat.operands_code(operands, type(self).__name__)
+        self.operands = operands
         self.trainable = bool(trainable)
         self.table = table
         self.k, self.init_dims, self.output_channels = table.k, table.init_dims, table.output_channels
@@ -143,8 +151,19 @@ class _TableNet(nn.Module):
         if self._packed is None or self._packed[0] != key:
             native = self._pack(conv, [(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps) for bn in bns],
                                 [(l.weight, l.bias) for l in lin])
+            if self.operands != "fp32":
+                native.set_operands(self.operands)
             self._packed = (key, native)
         return self._packed[1]
+
+    def set_operands(self, operands):
+        """"bf16": eval() runs the convolutions' GEMMs on bf16 operands with float32 accumulation; "fp32": the default.
+        Anything else is a ValueError.  train() is float32 whatever this says."""
+        _nat.operands_code(operands, type(self).__name__)
+        self.operands = operands
+        if self._packed is not None:
+            self._packed[1].set_operands(operands)
+        return self
 
     def _check_inputs(self, inputs):
         name = type(self).__name__
@@ -212,14 +231,14 @@ class _TableNet(nn.Module):
 
 
 class DGCNN(_TableNet):
-    def __init__(self, k, init_dims, emb_dims, dropout, output_channels=3, *, trainable=False):
+    def __init__(self, k, init_dims, emb_dims, dropout, output_channels=3, *, trainable=False, operands="fp32"):
         super().__init__()
         if int(init_dims) != 17:
             raise ValueError(f"DGCNN: init_dims must be 17 (forward takes rows 0:17 of its input), got {init_dims}")
         if not 1 <= int(k) <= 64:
             raise ValueError(f"DGCNN: k must be in [1, 64], got {k}")
         self.emb_dims = int(emb_dims)
-        self._build(_nat.DgcnnTable.fixed(k, emb_dims, output_channels), dropout, trainable)
+        self._build(_nat.DgcnnTable.fixed(k, emb_dims, output_channels), dropout, trainable, operands)
 
     def _pack(self, conv, bn, lin):
         return _nat.Dgcnn(conv, bn, lin, self.k, self.init_dims, self.emb_dims, self.output_channels)
@@ -241,7 +260,8 @@ class BetterDGCNN(_TableNet):
     _HEAD_SLOPE = 0.01               # F.leaky_relu's default: GCNModel.py:291 passes no slope
     _HEAD_BN_WIDE = True             # (DGCNN keeps its float32 head: its train() bits are the earlier ones)
 
-    def __init__(self, l_e, l_d, l_l, channel_sizes, k, init_dims, dropout, output_channels=3, *, trainable=False):
+    def __init__(self, l_e, l_d, l_l, channel_sizes, k, init_dims, dropout, output_channels=3, *, trainable=False,
+                 operands="fp32"):
         super().__init__()
         table = _nat.DgcnnTable(l_e, l_d, l_l, channel_sizes, k, init_dims, output_channels)
         self.l_e, self.l_d, self.l_l = table.l_e, table.l_d, table.l_l
@@ -249,7 +269,7 @@ class BetterDGCNN(_TableNet):
             torch.tensor(table.sizes, dtype=torch.int64)
         self.cum_sizes = F.pad(torch.cumsum(self.channel_sizes, 0), (1, 0), "constant", value=0)
         self.emb_dims = table.emb
-        self._build(table, dropout, trainable)
+        self._build(table, dropout, trainable, operands)
 
     def _pack(self, conv, bn, lin):
         return _nat.BetterDgcnn(self.table, conv, bn, lin)

@@ -15,6 +15,10 @@
 //                  B = (W_b - W_a) X come from one GEMM: W [x_j - x_i ; x_i] = W_a x_j + (W_b - W_a) x_i.
 //   fused_edge_kernel   that GEMM and edge_kernel in one launch for a layer with 2 Cout <= 128: the patch's [A ; B]
 //                  tile stays in LDS (BetterDGCNN's narrow layers; DGCNN keeps the two kernels).  The same bits.
+//   gemm_bf16_kernel, fused_edge_bf16_kernel   the opt-in bf16-operand mode (pcd_dgcnn_set_operands): the conv-form
+//                  GEMM and the fused layer on v_mfma_f32_32x32x16_bf16 -- operands rounded to bf16, float32 sums,
+//                  the float32 epilogues unchanged.  Edge layers with Cin >= 32 and the pooled convolution use them;
+//                  the first layer, the head, the searches and train() stay float32.
 //
 // Every output element depends on its own patch only and is summed in a fixed order: a patch's output bits do not
 // depend on the batch, its place in it, or the run.  No float atomics.  The library's -ffp-contract=off stays; where a
@@ -352,8 +356,214 @@ __global__ __launch_bounds__(256) void fused_edge_kernel(FusedEdgeArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------- bf16 operands, float32 accumulation
+// The opt-in arm of the conv-form GEMM on v_mfma_f32_32x32x16_bf16: the same 128 x 64 output tile (one column tile =
+// one patch), K tiles of 64.  The weight is rounded once on the host side of the mode switch into Wb [M][Kp], k
+// contiguous and zero-padded to Kp = 8 ceil(K / 8), so a lane's 8-k fragment is one 16-byte load; X stays float32 in
+// memory and is rounded (the plain cast: nearest even, NaN and Inf kept) on its way into LDS.  LDS rows are 72 bf16
+// (144 bytes = 36 banks): the 16-byte fragment reads of 16 consecutive rows start in 16 different groups of 4 banks.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+constexpr int BKH = 64, LDH = 72;
+static_assert(BM * 65 * 4 >= (BM + BN) * LDH * 2, "the pooling staging must cover the bf16 k tiles");
+
+struct GemmBf16Args {
+    const __bf16* Wb;       // [M][Kp]
+    const float* X;         // [b][K][64], patch stride xgs
+    float* Y;               // [b][M][64], patch stride ygs
+    const float* s;         // [M] (affine epilogues)
+    const float* t;
+    float* poolT;           // EPI_POOL: [2 M][b]
+    float* pool_dbg;        // EPI_POOL, nullable: [b][2 M]
+    int64_t xgs, ygs, b;
+    int M, K, Kp, epi;
+    float slope;
+};
+
+// float32 src(m, k) = src[m * sm + k * sk] -> Wb [M][Kp], zeros for k >= K
+__global__ void pack_bf16_kernel(const float* src, int64_t sm, int64_t sk, int M, int K, int Kp, __bf16* Wb) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)M * Kp) return;
+    const int m = (int)(e / Kp), k = (int)(e % Kp);
+    Wb[e] = k < K ? (__bf16)src[m * sm + k * sk] : (__bf16)0.f;
+}
+
+// conv weight W [Cout][2 Cin] -> the float32 [W_a ; W_b - W_a] of pack_edge, rounded, as Wb [2 Cout][Kp]
+__global__ void pack_edge_bf16_kernel(const float* W, int Cin, int Cout, int Kp, __bf16* Wb) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)2 * Cout * Kp) return;
+    const int m = (int)(e / Kp), k = (int)(e % Kp), c = m < Cout ? m : m - Cout;
+    float v = 0.f;
+    if (k < Cin) {
+        const float wa = W[(int64_t)c * 2 * Cin + k];
+        v = m < Cout ? wa : W[(int64_t)c * 2 * Cin + Cin + k] - wa;
+    }
+    Wb[e] = (__bf16)v;
+}
+
+// acc = rows m0 .. m0 + 127 of Wb times patch Xp [K][64]: the k loop both bf16 kernels run, so a fused layer has the
+// two-kernel path's bits.  lds: (BM + BN) * LDH bf16.  Every access past M or K is predicated: zeros enter the sum.
+__device__ __forceinline__ void bf16_tile(const __bf16* Wb, int M, int K, int Kp, int m0, const float* Xp, __bf16* lds,
+                                          f32x16 (&acc)[2]) {
+    __bf16* As = lds;                                  // [BM][LDH]
+    __bf16* Bs = lds + BM * LDH;                       // [BN][LDH]: X transposed, k contiguous
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;
+    // global -> LDS: 16-byte chunk tid + 256 r of the W tile (row chunk >> 3, k group chunk & 7); column tid & 63 of
+    // the X tile, k groups (tid >> 6) and (tid >> 6) + 4
+    const int xcol = tid & 63, xg0 = tid >> 6;
+    bf16x8 wr[4];
+    float xr[16];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = tid + 256 * r, m = m0 + (c >> 3), k = k0 + (c & 7) * 8;
+            bf16x8 z = {};
+            wr[r] = (m < M && k < Kp) ? *reinterpret_cast<const bf16x8*>(Wb + (int64_t)m * Kp + k) : z;
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = k0 + (xg0 + 4 * g) * 8 + j;
+                xr[8 * g + j] = k < K ? Xp[(int64_t)k * NODES + xcol] : 0.f;
+            }
+    };
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+    fetch(0);
+    const int arow = lane >> 5, acol = lane & 31;
+    for (int k0 = 0; k0 < K; k0 += BKH) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = tid + 256 * r;
+            *reinterpret_cast<bf16x8*>(As + (c >> 3) * LDH + (c & 7) * 8) = wr[r];
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            bf16x8 v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (__bf16)xr[8 * g + j];
+            *reinterpret_cast<bf16x8*>(Bs + xcol * LDH + (xg0 + 4 * g) * 8) = v;
+        }
+        __syncthreads();
+        if (k0 + BKH < K) fetch(k0 + BKH);
+#pragma unroll
+        for (int ks = 0; ks < BKH; ks += 16) {
+            if (k0 + ks >= K) break;                   // (uniform: the rest of the tile is zeros)
+            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(As + (wm + acol) * LDH + ks + 8 * arow);
+            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(As + (wm + 32 + acol) * LDH + ks + 8 * arow);
+            const bf16x8 bv = *reinterpret_cast<const bf16x8*>(Bs + (wn + acol) * LDH + ks + 8 * arow);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bv, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bv, acc[1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+}
+
+// gemm_kernel<0>'s epilogues on the bf16 product (plain, affine, affine + LeakyReLU, pool): float32, the same order
+__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmBf16Args a) {
+    __shared__ __attribute__((aligned(16))) float lds[BM * 65];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;
+    // one patch per column tile; the row tiles of a patch are neighbours in the grid, so they run together and the
+    // patch's X is read from memory once (patch-major order streamed X once per row tile: 8 GB for conv7 on 4096
+    // patches, which bounded the kernel)
+    const int mtiles = (a.M + BM - 1) / BM;
+    const int m0 = (int)(blockIdx.x % mtiles) * BM;
+    const int64_t p = blockIdx.x / mtiles;
+    f32x16 acc[2];
+    bf16_tile(a.Wb, a.M, a.K, a.Kp, m0, a.X + p * a.xgs, reinterpret_cast<__bf16*>(lds), acc);
+    const int arow = lane >> 5, acol = lane & 31;
+    const int cn = wn + acol;
+    float* Ps = lds;                                   // EPI_POOL: [BM][65] staging (every wave is past the k loop)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rm = mfma_row(wm + 32 * h, r, arow);
+            const int m = m0 + rm;
+            float v = acc[h][r];
+            if (a.epi != EPI_PLAIN && m < a.M) {
+                v = fmaf(a.s[m], v, a.t[m]);
+                if (a.epi != EPI_AFFINE) v = lrelu(v, a.slope);
+            }
+            if (a.epi == EPI_POOL)
+                Ps[rm * 65 + cn] = v;
+            else if (m < a.M)
+                a.Y[p * a.ygs + (int64_t)m * NODES + cn] = v;
+        }
+    }
+    if (a.epi != EPI_POOL) return;
+    __syncthreads();
+    // one row per 4 threads, 16 columns each in column order, then ((q0 + q1) + (q2 + q3)): a fixed-order sum
+    const int q = tid & 3;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int pr = half * 64 + (tid >> 2);
+        float sum = 0.f, mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float v = Ps[pr * 65 + q * 16 + c];
+            sum += v;
+            mx = nanmax(mx, v);
+        }
+        sum += __shfl_xor(sum, 1);
+        mx = nanmax(mx, __shfl_xor(mx, 1));
+        sum += __shfl_xor(sum, 2);
+        mx = nanmax(mx, __shfl_xor(mx, 2));
+        const int m = m0 + pr;
+        if (q == 0 && m < a.M) {
+            const float mean = sum * (1.f / NODES);
+            a.poolT[(int64_t)m * a.b + p] = mx;
+            a.poolT[((int64_t)a.M + m) * a.b + p] = mean;
+            if (a.pool_dbg) {
+                a.pool_dbg[p * 2 * a.M + m] = mx;
+                a.pool_dbg[p * 2 * a.M + a.M + m] = mean;
+            }
+        }
+    }
+}
+
+// fused_edge_kernel on the bf16 product: Wb [2 Cout][Kp]
+struct FusedEdgeBf16Args {
+    const __bf16* Wb;
+    const float* X;
+    const int32_t* lists;
+    const float *s, *t;
+    float* out;
+    int64_t xgs, ogs;
+    int Cin, Kp, Cout, kk;
+};
+
+__global__ __launch_bounds__(256) void fused_edge_bf16_kernel(FusedEdgeBf16Args a) {
+    __shared__ __attribute__((aligned(16))) float lds[BM * 65];   // the K tiles; afterwards the [BM][65] tile of P
+    __shared__ uint8_t nbr[NODES * NODES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32;
+    const int64_t p = blockIdx.x;
+    for (int e = tid; e < NODES * a.kk; e += 256) nbr[e] = (uint8_t)(a.lists[p * NODES * a.kk + e] & 63);
+    f32x16 acc[2];
+    bf16_tile(a.Wb, 2 * a.Cout, a.Cin, a.Kp, 0, a.X + p * a.xgs, reinterpret_cast<__bf16*>(lds), acc);
+    float* Ps = lds;
+    const int arow = lane >> 5, cn = wn + (lane & 31);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ps[mfma_row(wm + 32 * h, r, arow) * 65 + cn] = acc[h][r];
+    __syncthreads();
+    const uint8_t* row = nbr + lane * a.kk;
+    for (int c = wave; c < a.Cout; c += 4) {
+        const float* A = Ps + c * 65;
+        const float Bi = Ps[(a.Cout + c) * 65 + lane];
+        const float sc = a.s[c], tc = a.t[c];
+        float m = -INFINITY;
+        for (int j = 0; j < a.kk; ++j) m = nanmax(m, fmaf(sc, A[row[j]] + Bi, tc));
+        a.out[p * a.ogs + (int64_t)c * NODES + lane] = lrelu(m);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- host side
-constexpr int kWideFlush = 8;       // k per float32 chain of the train-mode forward products
+constexpr int kWideFlush = 8;      // k per float32 chain of the train-mode forward products
 
 int launch_gemm(const GemmArgs& a, hipStream_t st, bool wide = false) {
     if (a.N <= 0 || a.M <= 0) return PCD_OK;
@@ -364,6 +574,30 @@ int launch_gemm(const GemmArgs& a, hipStream_t st, bool wide = false) {
         hipLaunchKernelGGL(gemm_kernel<0>, grid, dim3(256), 0, st, a);
     PCD_LAUNCH_CHECK();
     return PCD_OK;
+}
+
+int launch_gemm_bf16(const GemmBf16Args& a, hipStream_t st) {
+    if (a.b <= 0 || a.M <= 0) return PCD_OK;
+    // (b <= 2^20 patches x at most 512 row tiles: the grid stays below 2^31)
+    hipLaunchKernelGGL(gemm_bf16_kernel, dim3((unsigned)(a.b * cdiv(a.M, BM))), dim3(256), 0, st, a);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+int padded_k(int K) { return (K + 7) / 8 * 8; }
+// float32 src(m, k) = src[m * sm + k * sk] -> Wb [M][padded_k(K)], rounded to nearest even
+int pack_bf16(const float* src, int64_t sm, int64_t sk, int M, int K, __bf16* Wb, hipStream_t st) {
+    const int Kp = padded_k(K);
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3((unsigned)cdiv((int64_t)M * Kp, 256)), dim3(256), 0, st, src, sm, sk, M,
+                       K, Kp, Wb);
+    PCD_LAUNCH_CHECK();
+    return PCD_OK;
+}
+GemmBf16Args conv_args_bf16(const __bf16* Wb, int M, int K, const float* X, int64_t xgs, float* Y, int64_t ygs,
+                            int64_t b) {
+    GemmBf16Args a{};
+    a.Wb = Wb; a.X = X; a.Y = Y; a.M = M; a.K = K; a.Kp = padded_k(K); a.b = b; a.xgs = xgs; a.ygs = ygs;
+    a.epi = EPI_PLAIN; a.slope = kTrunkSlope;
+    return a;
 }
 
 // conv form: X [b][K][64] (patch stride xgs) -> Y [b][M][64] (patch stride ygs)
@@ -391,6 +625,12 @@ struct pcd_dgcnn {
     // transposed weights and folded batch norms (s, t), in network order: the E edge layers [Cin][2 Cout], the pooled
     // convolution [Ccat][emb], the l_l linears; the last linear's (s, t) is (1, bias)
     std::vector<const float*> wt, s, t;
+    // PCD_OPERANDS_BF16: the trunk's weights rounded to bf16, [M][padded_k(K)] each, made at the first switch; null
+    // for a layer that stays on the float32 kernel
+    int operands = PCD_OPERANDS_F32;
+    __bf16* dev16 = nullptr;
+    std::vector<const __bf16*> wb;
+    const __bf16* bf16_weight(int l) const { return operands == PCD_OPERANDS_BF16 ? wb[l] : nullptr; }
 };
 
 namespace {
@@ -430,16 +670,29 @@ Workspace layout(const Net& n, int64_t b, void* ws) {
     return w;
 }
 
-// out: the layer's output [b][Cout][64], patch stride e.ogs.  fused: P is not touched.
-int run_edge(const float* wt, const float* s, const float* t, const EdgeLayer& e, float* P, float* out, int64_t b,
-             bool fused, hipStream_t st) {
+// The smallest Cin of an edge layer that the bf16 mode moves to the bf16 kernel: below it (the first layer's 17 rows)
+// K does not fill one bf16 k-step and the layer keeps the float32 kernel.
+constexpr int kBf16MinCin = 32;
+
+// out: the layer's output [b][Cout][64], patch stride e.ogs.  fused: P is not touched.  wb not null: the product on
+// the bf16 kernel from wb [2 Cout][padded_k(Cin)]; wt is not read.
+int run_edge(const float* wt, const __bf16* wb, const float* s, const float* t, const EdgeLayer& e, float* P,
+             float* out, int64_t b, bool fused, hipStream_t st) {
+    if (fused && wb) {
+        FusedEdgeBf16Args a{wb, e.X, e.lists, s, t, out, e.xgs, e.ogs, e.Cin, padded_k(e.Cin), e.Cout, e.kk};
+        hipLaunchKernelGGL(fused_edge_bf16_kernel, dim3((unsigned)b), dim3(256), 0, st, a);
+        PCD_LAUNCH_CHECK();
+        return PCD_OK;
+    }
     if (fused) {
         FusedEdgeArgs a{wt, e.X, e.lists, s, t, out, e.xgs, e.ogs, e.Cin, e.Cout, e.kk};
         hipLaunchKernelGGL(fused_edge_kernel, dim3((unsigned)b), dim3(256), 0, st, a);
         PCD_LAUNCH_CHECK();
         return PCD_OK;
     }
-    const int rc = launch_gemm(conv_args(wt, 2 * e.Cout, e.Cin, e.X, e.xgs, P, (int64_t)2 * e.Cout * NODES, b), st);
+    const int64_t pgs = (int64_t)2 * e.Cout * NODES;
+    const int rc = wb ? launch_gemm_bf16(conv_args_bf16(wb, 2 * e.Cout, e.Cin, e.X, e.xgs, P, pgs, b), st)
+                      : launch_gemm(conv_args(wt, 2 * e.Cout, e.Cin, e.X, e.xgs, P, pgs, b), st);
     if (rc != PCD_OK) return rc;
     hipLaunchKernelGGL(edge_kernel, dim3((unsigned)b, (unsigned)cdiv(e.Cout, 4)), dim3(256), 0, st, P, e.Cout, e.lists,
                        e.kk, s, t, out, e.ogs);
@@ -695,9 +948,16 @@ static int forward_impl(const pcd_dgcnn* m, const float* inputs, int64_t b, floa
         const EdgeLayer e = edge_layer(n, l, inputs, w.cat, w.idx3, w.knn, b);
         if (e.knn && (rc = dgcnn::knn(e.X, e.xgs, e.Cin, e.kk, e.knn, b, st)) != PCD_OK) return rc;
         const bool fused = fused_layer(n, l);
-        if ((rc = run_edge(m->wt[l], m->s[l], m->t[l], e, w.P, w.cat + e.out_off, b, fused, st)) != PCD_OK) return rc;
+        rc = run_edge(m->wt[l], m->bf16_weight(l), m->s[l], m->t[l], e, w.P, w.cat + e.out_off, b, fused, st);
+        if (rc != PCD_OK) return rc;
     }
-    {   // the pooled convolution + batch norm + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
+    // the pooled convolution + batch norm + LeakyReLU + max / mean over the nodes -> pooled [2 emb][b]
+    if (const __bf16* wb = m->bf16_weight(E)) {
+        GemmBf16Args a = conv_args_bf16(wb, n.emb, n.Ccat, w.cat, n.cat_stride(), nullptr, 0, b);
+        a.epi = EPI_POOL; a.s = m->s[E]; a.t = m->t[E]; a.poolT = w.pooled;
+        a.pool_dbg = debug ? debug->pooled : nullptr;
+        if ((rc = launch_gemm_bf16(a, st)) != PCD_OK) return rc;
+    } else {
         GemmArgs a = conv_args(m->wt[E], n.emb, n.Ccat, w.cat, n.cat_stride(), nullptr, 0, b);
         a.epi = EPI_POOL; a.s = m->s[E]; a.t = m->t[E]; a.poolT = w.pooled;
         a.pool_dbg = debug ? debug->pooled : nullptr;
@@ -780,7 +1040,57 @@ int pcd_bdgcnn_create(const pcd_dgcnn_table* t, const pcd_bdgcnn_weights* w, pcd
 int pcd_dgcnn_destroy(pcd_dgcnn* m) {
     if (!m) return PCD_OK;
     if (m->dev) (void)hipFree(m->dev);
+    if (m->dev16) (void)hipFree(m->dev16);
     delete m;
+    return PCD_OK;
+}
+
+int pcd_dgcnn_set_operands(pcd_dgcnn* m, int operands) {
+    PCD_CHECK_ARG(operands == PCD_OPERANDS_F32 || operands == PCD_OPERANDS_BF16,
+                  "operands must be PCD_OPERANDS_F32 or PCD_OPERANDS_BF16");
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    if (operands == PCD_OPERANDS_BF16 && !m->dev16) {
+        // the packed float32 [W_a ; W_b - W_a] of every edge layer with Cin >= 32, and W7, rounded once
+        const Net& n = m->net;
+        const int E = n.E;
+        std::vector<int64_t> off(E + 1, -1);
+        Carver c{nullptr};
+        for (int l = 0; l <= E; ++l) {
+            if (l < E && n.Cin[l] < kBf16MinCin) continue;
+            const int M = l < E ? 2 * n.Cout[l] : n.emb, K = l < E ? n.Cin[l] : n.Ccat;
+            off[l] = c.take((int64_t)M * padded_k(K) * 2);
+        }
+        __bf16* dev16 = nullptr;
+        hipError_t e = hipMalloc((void**)&dev16, c.used > 0 ? c.used : 256);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? PCD_ERR_OOM : PCD_ERR_HIP,
+                        std::string("pcd_dgcnn_set_operands: ") + hipGetErrorString(e));
+        std::vector<const __bf16*> wb(E + 1, nullptr);
+        int rc = PCD_OK;
+        for (int l = 0; l <= E && rc == PCD_OK; ++l) {
+            if (off[l] < 0) continue;
+            const int M = l < E ? 2 * n.Cout[l] : n.emb, K = l < E ? n.Cin[l] : n.Ccat;
+            __bf16* dst = at<__bf16>(dev16, off[l]);
+            rc = pack_bf16(m->wt[l], 1, M, M, K, dst, nullptr);      // Wt [K][M]
+            wb[l] = dst;
+        }
+        if (rc == PCD_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess)
+            rc = fail(PCD_ERR_HIP, std::string("pcd_dgcnn_set_operands: ") + hipGetErrorString(e));
+        if (rc != PCD_OK) {
+            (void)hipFree(dev16);
+            return rc;
+        }
+        m->dev16 = dev16;
+        m->wb = wb;
+    }
+    m->operands = operands;
+    return PCD_OK;
+}
+
+int pcd_dgcnn_operands(const pcd_dgcnn* m, int* operands) {
+    PCD_CHECK_ARG(m != nullptr, "model is null");
+    PCD_CHECK_ARG(operands != nullptr, "operands is null");
+    *operands = m->operands;
     return PCD_OK;
 }
 int pcd_bdgcnn_destroy(pcd_dgcnn* m) { return pcd_dgcnn_destroy(m); }
@@ -850,7 +1160,8 @@ int pcd_dgcnn_edgeconv(const pcd_dgcnn* m, int layer, const float* x, int64_t b,
     StreamTemps tmp(st);
     float* P;
     PCD_HIP(tmp.alloc(&P, b * 2 * Cout * NODES * sizeof(float)));
-    const int rc = run_edge(m->wt[l], m->s[l], m->t[l], edge_layer_alone(Cin, Cout, x, lists, list_len), P, out, b, false, st);
+    const int rc = run_edge(m->wt[l], m->bf16_weight(l), m->s[l], m->t[l],
+                            edge_layer_alone(Cin, Cout, x, lists, list_len), P, out, b, false, st);
     if (rc != PCD_OK) return rc;
     PCD_HIP(tmp.release());
     return PCD_OK;
@@ -863,6 +1174,13 @@ static int64_t edgeconv_scratch(int c_in, int c_out, int64_t b, bool fused, void
     *P = fused ? nullptr : c.carve<float>(b * 2 * c_out * NODES * 4);
     return c.used;
 }
+// the bf16 stage entry's: the rounded weight [2 c_out][padded_k(c_in)] in the packed weight's place, then P
+static int64_t edgeconv_scratch_bf16(int c_in, int c_out, int64_t b, bool fused, void* base, __bf16** wb, float** P) {
+    Carver c{base};
+    *wb = c.carve<__bf16>((int64_t)2 * c_out * padded_k(c_in) * 2);
+    *P = fused ? nullptr : c.carve<float>(b * 2 * c_out * NODES * 4);
+    return c.used;
+}
 
 int pcd_bdgcnn_edgeconv_scratch_bytes(int c_in, int c_out, int64_t b, int64_t* bytes) {
     PCD_CHECK_ARG(bytes != nullptr, "bytes is null");
@@ -870,7 +1188,11 @@ int pcd_bdgcnn_edgeconv_scratch_bytes(int c_in, int c_out, int64_t b, int64_t* b
                   "c_in and c_out must be in [1, " + std::to_string(kMaxEdgeWidth) + "]");
     PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
     float *wt, *P;
+    __bf16* wb;
     *bytes = edgeconv_scratch(c_in, c_out, b, false, nullptr, &wt, &P);
+    // (the bf16 weight's rows are padded to 8 k: longer than the float32 weight only where c_in < 7)
+    const int64_t bf = edgeconv_scratch_bf16(c_in, c_out, b, false, nullptr, &wb, &P);
+    if (bf > *bytes) *bytes = bf;
     return PCD_OK;
 }
 
@@ -904,9 +1226,74 @@ int pcd_bdgcnn_edgeconv(const float* w, const float* s, const float* t, int c_in
     }
     int rc = dgcnn::pack_edge(w, c_in, c_out, wt, nullptr, st);
     if (rc != PCD_OK) return rc;
-    rc = run_edge(wt, s, t, edge_layer_alone(c_in, c_out, x, lists, list_len), P, out, b, fuse, st);
+    rc = run_edge(wt, nullptr, s, t, edge_layer_alone(c_in, c_out, x, lists, list_len), P, out, b, fuse, st);
     if (rc != PCD_OK) return rc;
     if (!scratch) PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+int pcd_bdgcnn_edgeconv_bf16(const float* w, const float* s, const float* t, int c_in, int c_out, const float* x,
+                             int64_t b, const int32_t* lists, int list_len, int fused, float* out, void* scratch,
+                             int64_t scratch_bytes, void* stream) {
+    PCD_CHECK_ARG(fused == PCD_FUSED_OFF || fused == PCD_FUSED_ON || fused == PCD_FUSED_AUTO,
+                  "fused must be PCD_FUSED_OFF, PCD_FUSED_ON or PCD_FUSED_AUTO");
+    PCD_CHECK_ARG(fused != PCD_FUSED_ON || 2 * c_out <= BM,
+                  "fused = PCD_FUSED_ON needs 2 c_out <= " + std::to_string(BM) + " (one GEMM tile holds the patch's [A ; B])");
+    PCD_CHECK_ARG(c_in >= 1 && c_in <= kMaxEdgeWidth && c_out >= 1 && c_out <= kMaxEdgeWidth,
+                  "c_in and c_out must be in [1, " + std::to_string(kMaxEdgeWidth) + "]");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(list_len >= 1 && list_len <= NODES, "list_len must be in [1, 64]");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(w && s && t && x && lists && out, "a pointer is null");
+    const bool fuse = fused == PCD_FUSED_ON || (fused == PCD_FUSED_AUTO && fused_wins(c_in, c_out, list_len));
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    __bf16* wb;
+    float* P;
+    const int64_t need = edgeconv_scratch_bf16(c_in, c_out, b, fuse, scratch, &wb, &P);
+    if (scratch) {
+        PCD_CHECK_ARG(scratch_bytes >= need && reinterpret_cast<uintptr_t>(scratch) % 16 == 0,
+                      "scratch must be 16-byte aligned and hold the " + std::to_string(need) +
+                          " bytes that pcd_bdgcnn_edgeconv_scratch_bytes asks for at most, got " +
+                          std::to_string(scratch_bytes));
+    } else {
+        char* own;
+        PCD_HIP(tmp.alloc(&own, need));
+        edgeconv_scratch_bf16(c_in, c_out, b, fuse, own, &wb, &P);
+    }
+    const int Kp = padded_k(c_in);
+    hipLaunchKernelGGL(pack_edge_bf16_kernel, dim3((unsigned)cdiv((int64_t)2 * c_out * Kp, 256)), dim3(256), 0, st, w,
+                       c_in, c_out, Kp, wb);
+    PCD_LAUNCH_CHECK();
+    const int rc = run_edge(nullptr, wb, s, t, edge_layer_alone(c_in, c_out, x, lists, list_len), P, out, b, fuse, st);
+    if (rc != PCD_OK) return rc;
+    if (!scratch) PCD_HIP(tmp.release());
+    return PCD_OK;
+}
+
+int pcd_dgcnn_gemm_bf16(const float* w, const float* x, int m_rows, int k_cols, int64_t b, int epilogue, const float* s,
+                        const float* t, float* y, void* stream) {
+    PCD_CHECK_ARG(m_rows >= 1 && k_cols >= 1, "M and K must be >= 1");
+    PCD_CHECK_ARG(b >= 0 && b <= kMaxBatch, "b must be in [0, 2^20]");
+    PCD_CHECK_ARG(epilogue >= EPI_PLAIN && epilogue <= EPI_AFFINE, "epilogue must be in [0, 3]");
+    PCD_CHECK_ARG(epilogue == EPI_PLAIN || (s != nullptr && t != nullptr), "s / t is null");
+    if (b == 0) return PCD_OK;
+    PCD_CHECK_ARG(w != nullptr && x != nullptr && y != nullptr, "w / x / y is null");
+    hipStream_t st = as_stream(stream);
+    StreamTemps tmp(st);
+    __bf16* Wb;
+    float* poolT = nullptr;
+    PCD_HIP(tmp.alloc(&Wb, (int64_t)m_rows * padded_k(k_cols) * 2));
+    int rc = pack_bf16(w, k_cols, 1, m_rows, k_cols, Wb, st);
+    if (rc != PCD_OK) return rc;
+    GemmBf16Args a = conv_args_bf16(Wb, m_rows, k_cols, x, (int64_t)k_cols * NODES, y, (int64_t)m_rows * NODES, b);
+    a.epi = epilogue; a.s = s; a.t = t;
+    if (epilogue == EPI_POOL) {                        // y [b][2 M]
+        PCD_HIP(tmp.alloc(&poolT, 2 * (int64_t)m_rows * b * sizeof(float)));
+        a.poolT = poolT; a.pool_dbg = y; a.Y = nullptr;
+    }
+    if ((rc = launch_gemm_bf16(a, st)) != PCD_OK) return rc;
+    PCD_HIP(tmp.release());
     return PCD_OK;
 }
 

@@ -244,6 +244,12 @@ _SIGS = {
     "pcd_bdgcnn_edgeconv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int,
                                     c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "pcd_bdgcnn_edgeconv_scratch_bytes": (c_int, [c_int, c_int, c_int64, POINTER(c_int64)]),
+    "pcd_dgcnn_set_operands": (c_int, [c_void_p, c_int]),
+    "pcd_dgcnn_operands": (c_int, [c_void_p, POINTER(c_int)]),
+    "pcd_dgcnn_gemm_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "pcd_bdgcnn_edgeconv_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int,
+                                         c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "pcd_bdgcnn_train_workspace_bytes": (c_int, [POINTER(DgcnnTableStruct), c_int64, POINTER(c_int64)]),
     "pcd_bdgcnn_train_forward": (c_int, [POINTER(DgcnnTableStruct), POINTER(BdgcnnTrainParams), c_void_p, c_int64,
                                          c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1180,6 +1186,14 @@ DGCNN_COUT = (64, 64, 128, 256, 256, 256)
 EPI_PLAIN, EPI_AFFINE_LRELU, EPI_POOL, EPI_AFFINE, EPI_ADD = range(5)
 host_packs = 0                       # how often Dgcnn() packed a model's weights through the host (pcd_dgcnn_create)
 DGCNN_NO_BAD_PATCH = 0x7f7f7f7f      # PCD_DGCNN_NO_BAD_PATCH
+OPERANDS = {"fp32": 0, "bf16": 1}    # PCD_OPERANDS_*
+
+
+def operands_code(operands, what="pcd") -> int:
+    """"fp32" / "bf16" -> PCD_OPERANDS_*; ValueError for anything else."""
+    if not isinstance(operands, str) or operands not in OPERANDS:
+        raise ValueError(f'{what}: operands must be "fp32" or "bf16", got {operands!r}')
+    return OPERANDS[operands]
 
 
 class DgcnnTable:
@@ -1315,6 +1329,19 @@ class Dgcnn:
             _lib.pcd_dgcnn_destroy(h)
             self.handle = None
 
+    def set_operands(self, operands: str):
+        """"bf16": the trunk's GEMMs (edge layers with Cin >= 32, the pooled convolution) take bf16 operands and
+        accumulate in float32; "fp32": the default (pcd_dgcnn_set_operands).  The first switch to bf16 rounds the
+        packed weights, synchronously."""
+        check(lib().pcd_dgcnn_set_operands(self.handle, operands_code(operands, f"pcd: {self._NAME}")),
+              "pcd_dgcnn_set_operands")
+
+    @property
+    def operands(self) -> str:
+        v = c_int(0)
+        check(lib().pcd_dgcnn_operands(self.handle, ctypes.byref(v)), "pcd_dgcnn_operands")
+        return {c: n for n, c in OPERANDS.items()}[v.value]
+
     def workspace_bytes(self, b: int) -> int:
         v = c_int64(0)
         check(lib().pcd_dgcnn_workspace_bytes(self.handle, int(b), ctypes.byref(v)), "pcd_dgcnn_workspace_bytes")
@@ -1436,12 +1463,14 @@ def bdgcnn_edgeconv_scratch_bytes(c_in: int, c_out: int, b: int) -> int:
     return v.value
 
 
-def bdgcnn_edgeconv(w, s, t, x, lists, fused: int = FUSED_AUTO, scratch=None, out=None):
+def bdgcnn_edgeconv(w, s, t, x, lists, fused: int = FUSED_AUTO, scratch=None, out=None, operands: str = "fp32"):
     """One edge layer in eval() by its shapes (pcd_bdgcnn_edgeconv): w [Cout, 2 Cin], the folded batch norm s, t
     [Cout], x [b, Cin, 64], lists int32 [b, 64, n] -> [b, Cout, 64].  fused: FUSED_OFF (GEMM, then the max over the
     lists), FUSED_ON (one kernel, 2 Cout <= 128 only) or FUSED_AUTO (the library's choice); the bits are the same.
     scratch: None, or a contiguous device tensor of bdgcnn_edgeconv_scratch_bytes(Cin, Cout, b) bytes -- then nothing
-    is allocated and nothing waits for the device; out: None or the float32 [b, Cout, 64] tensor to write."""
+    is allocated and nothing waits for the device; out: None or the float32 [b, Cout, 64] tensor to write.
+    operands = "bf16": the product on the bf16 kernel, whatever Cin is (pcd_bdgcnn_edgeconv_bf16)."""
+    bf16 = operands_code(operands, "pcd: bdgcnn_edgeconv") == OPERANDS["bf16"]
     w, s, t, x, lists = f32(w), f32(s), f32(t), f32(x), on_device(lists, torch.int32)
     w = w.reshape(w.shape[0], -1)
     b, cout = x.size(0), w.size(0)
@@ -1458,9 +1487,10 @@ def bdgcnn_edgeconv(w, s, t, x, lists, fused: int = FUSED_AUTO, scratch=None, ou
             or not out.is_contiguous():
         raise ValueError(f"pcd: bdgcnn_edgeconv: out must be float32 [{b}, {cout}, 64] contiguous on {x.device}")
     nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    check(lib().pcd_bdgcnn_edgeconv(ptr(w), ptr(s), ptr(t), x.size(1), cout, ptr(x), b, ptr(lists), lists.size(2),
-                                    int(fused), ptr(out), ptr(scratch), nbytes, c_void_p(stream_ptr())),
-          "pcd_bdgcnn_edgeconv")
+    entry, name = ((lib().pcd_bdgcnn_edgeconv_bf16, "pcd_bdgcnn_edgeconv_bf16") if bf16 else
+                   (lib().pcd_bdgcnn_edgeconv, "pcd_bdgcnn_edgeconv"))
+    check(entry(ptr(w), ptr(s), ptr(t), x.size(1), cout, ptr(x), b, ptr(lists), lists.size(2), int(fused), ptr(out),
+                ptr(scratch), nbytes, c_void_p(stream_ptr())), name)
     return out
 
 
@@ -1503,6 +1533,22 @@ def dgcnn_gemm(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=No
         y = torch.empty(shape, dtype=torch.float32, device=x.device)
     check(lib().pcd_dgcnn_gemm(ptr(w), ptr(x), M, K, b, nodes, int(epilogue), ptr(s), ptr(t), ptr(y),
                                c_void_p(stream_ptr())), "pcd_dgcnn_gemm")
+    return y
+
+
+def dgcnn_gemm_bf16(w: torch.Tensor, x: torch.Tensor, epilogue: int = EPI_PLAIN, s=None, t=None) -> torch.Tensor:
+    """dgcnn_gemm for x [b, K, 64] on the bf16 kernel (pcd_dgcnn_gemm_bf16): float32 w and x are rounded to bf16 as the
+    forward in bf16 mode rounds them, the products accumulated in float32.  Epilogues 0-3."""
+    w, x = f32(w), f32(x)
+    M, K = w.shape
+    b = x.size(0)
+    if x.dim() != 3 or tuple(x.shape) != (b, K, 64):
+        raise ValueError(f"pcd: dgcnn_gemm_bf16: x {tuple(x.shape)} does not fit w {tuple(w.shape)}")
+    s = None if s is None else f32(s)
+    t = None if t is None else f32(t)
+    y = torch.empty((b, 2 * M) if epilogue == EPI_POOL else (b, M, 64), dtype=torch.float32, device=x.device)
+    check(lib().pcd_dgcnn_gemm_bf16(ptr(w), ptr(x), M, K, b, int(epilogue), ptr(s), ptr(t), ptr(y),
+                                    c_void_p(stream_ptr())), "pcd_dgcnn_gemm_bf16")
     return y
 
 

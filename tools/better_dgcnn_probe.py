@@ -3,6 +3,7 @@
 and one training step of two networks, each next to the same network as torch-eager modules on the same device.
 
   python tools/better_dgcnn_probe.py [--chunk 4096] [--train-batch 256] [--repeat 5] [--eager-repeat 3]
+                                     [--operands fp32|bf16]
 
 Everything is timed between HIP events on the current stream: one warm-up, then --repeat runs; median and spread
 (max - min of the runs).
@@ -18,6 +19,8 @@ Everything is timed between HIP events on the current stream: one warm-up, then 
   eager      the same modules as plain torch ops (the edge tensors [b, 2 C, 64, n] materialised)
 The inputs are random features with valid index columns and the weights torch's default initialisation: the time
 does not depend on them.  One JSON line.
+--operands bf16 runs the fused comparison and eval() in the opt-in bf16-operand mode (pcd_bdgcnn_edgeconv_bf16, the
+models built with operands="bf16"); train() is float32 whatever it says.
 """
 import argparse
 import json
@@ -85,10 +88,10 @@ def random_inputs(b, dev, seed=0):
     return x.to(dev)
 
 
-def build(name, dev, trainable):
+def build(name, dev, trainable, operands="fp32"):
     l_e, l_d, l_l, sizes, k = NETWORKS[name]
     torch.manual_seed(0)
-    model = BetterDGCNN(l_e, l_d, l_l, sizes, k, 17, 0.0, trainable=trainable)
+    model = BetterDGCNN(l_e, l_d, l_l, sizes, k, 17, 0.0, trainable=trainable, operands=operands)
     for key, buf in model.named_buffers():
         if key.endswith("running_var"):
             buf.uniform_(0.5, 1.5)
@@ -138,10 +141,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--eager-repeat", type=int, default=3)
     ap.add_argument("--inner", type=int, default=20, help="calls per timed window of the fused comparison")
+    ap.add_argument("--operands", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     dev = nat.device()
-    res = {"build": nat.build_id(), "chunk": a.chunk, "train_batch": a.train_batch, "repeat": a.repeat, "fused": [],
-           "eval": {}, "train": {}}
+    res = {"build": nat.build_id(), "operands": a.operands, "chunk": a.chunk, "train_batch": a.train_batch,
+           "repeat": a.repeat, "fused": [], "eval": {}, "train": {}}
 
     g = torch.Generator(device="cpu").manual_seed(1)
     for cin, cout, n in FUSED_SHAPES:
@@ -152,8 +156,9 @@ def main():
         scratch = torch.empty(nat.bdgcnn_edgeconv_scratch_bytes(cin, cout, a.chunk), dtype=torch.uint8, device=dev)
         outs = [torch.empty((a.chunk, cout, 64), dtype=torch.float32, device=dev) for _ in range(2)]
         off, on = measure_alternating(
-            [lambda: nat.bdgcnn_edgeconv(w, s, t, x, lists, nat.FUSED_OFF, scratch, outs[0]),
-             lambda: nat.bdgcnn_edgeconv(w, s, t, x, lists, nat.FUSED_ON, scratch, outs[1])], a.repeat, a.inner)
+            [lambda: nat.bdgcnn_edgeconv(w, s, t, x, lists, nat.FUSED_OFF, scratch, outs[0], a.operands),
+             lambda: nat.bdgcnn_edgeconv(w, s, t, x, lists, nat.FUSED_ON, scratch, outs[1], a.operands)],
+            a.repeat, a.inner)
         same = torch.equal(outs[0], outs[1])
         del scratch, outs, x, lists
         res["fused"].append({"cin": cin, "cout": cout, "list_len": n, "two_kernels_ms": off, "fused_ms": on,
@@ -161,7 +166,7 @@ def main():
                              "wins": on["max"] < off["min"]})
 
     for name in NETWORKS:
-        model = build(name, dev, False).eval()
+        model = build(name, dev, False, a.operands).eval()
         x = random_inputs(a.chunk, dev)
         ws = model.native().workspace(a.chunk)
         flag = torch.full((1,), nat.DGCNN_NO_BAD_PATCH, dtype=torch.int32, device=dev)

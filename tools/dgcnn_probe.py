@@ -3,7 +3,7 @@
 through a plain torch-eager statement of the network on the same device.
 
   python tools/dgcnn_probe.py [--mesh data/stanford_bunny_mesh.npz] [--faces N] [--chunk 4096] [--k 8] [--emb 1024]
-                              [--repeat 5] [--eager-repeat 3]
+                              [--repeat 5] [--eager-repeat 3] [--operands fp32|bf16]
 
 Per pass over the faces, each stage between HIP events on the current stream (one warm-up pass first, then --repeat
 passes; best and median):
@@ -14,6 +14,9 @@ and, on the first chunk alone, the forward's parts through the stage entries (pc
 with the forward's own debug tensors, and the eager network.  TFLOP/s counts 182 MFLOP per patch at emb = 1024 (the 91 M
 multiply-adds of the GEMMs after splitting the edge weight, the searches not counted; the eager network does 240 M).  The weights are random (torch's default
 initialisation, random running statistics): the time does not depend on them.  One JSON line.
+--operands bf16 times the opt-in mode (bf16 GEMM operands, float32 accumulation): the model, the edge layers and the
+pooled convolution's stage entry (pcd_dgcnn_gemm_bf16) then run the bf16 kernel; the eager network stays float32, so
+eager_vs_hip_* then shows what the mode costs in precision.
 """
 import argparse
 import json
@@ -116,6 +119,7 @@ def main():
     ap.add_argument("--emb", type=int, default=1024)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--eager-repeat", type=int, default=3)
+    ap.add_argument("--operands", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     dev = nat.device()
     d = np.load(a.mesh)
@@ -124,7 +128,7 @@ def main():
     n = len(f) if a.faces <= 0 else min(a.faces, len(f))
     fis = np.arange(n)
     torch.manual_seed(0)
-    model = DGCNN(a.k, 17, a.emb, 0.5)
+    model = DGCNN(a.k, 17, a.emb, 0.5, operands=a.operands)
     for name, buf in model.named_buffers():
         if name.endswith("running_var"):
             buf.uniform_(0.5, 1.5)
@@ -137,7 +141,8 @@ def main():
     fn = mesh._geometry()[6].to(torch.float64)
     one_pass(pc, model, fis, chunk, ws, fn)                            # warm-up: code objects, caches, the topology
     runs = [one_pass(pc, model, fis, chunk, ws, fn) for _ in range(a.repeat)]
-    res = {"mesh": os.path.basename(a.mesh), "faces": len(f), "patches": n, "chunk": chunk, "k": a.k, "emb": a.emb,
+    res = {"build": nat.build_id(), "operands": a.operands, "mesh": os.path.basename(a.mesh), "faces": len(f),
+           "patches": n, "chunk": chunk, "k": a.k, "emb": a.emb,
            "repeat": a.repeat, "workspace_MB": round(ws.numel() / 2 ** 20, 1)}
     for stage in ("input", "forward", "unalign"):
         ts = [r[stage] for r in runs]
@@ -170,7 +175,8 @@ def main():
         part(f"edgeconv{layer}", lambda: native.edgeconv(layer, xin, lists))
     w7 = model.conv7[0].weight.detach().reshape(a.emb, 1024)
     one = torch.ones(a.emb, device=dev)
-    part("conv7_pool", lambda: nat.dgcnn_gemm(w7, cat, nat.EPI_POOL, one, one))
+    conv7 = nat.dgcnn_gemm_bf16 if a.operands == "bf16" else nat.dgcnn_gemm
+    part("conv7_pool", lambda: conv7(w7, cat, nat.EPI_POOL, one, one))
     part("forward_chunk", lambda: model(x, workspace=ws))
     flag = torch.full((1,), nat.DGCNN_NO_BAD_PATCH, dtype=torch.int32, device=dev)
     part("forward_chunk_deferred", lambda: model(x, workspace=ws, first_bad=flag))
