@@ -107,18 +107,28 @@ int pcd_grid_get_info(const pcd_grid* g, pcd_grid_info_t* out);
 int pcd_grid_perm(const pcd_grid* g, int32_t* perm, void* stream);
 
 /* ------------------------------------------------------------------ kNN (H2) */
-/* For each query row q[nq][3] the k nearest snapshot points, ascending (d², index).
+/* For each query row q[nq][3] the k nearest snapshot points, ascending (d², index): d² is the fp32
+ * ((dx·dx) + (dy·dy)) + (dz·dz) of dx = q.x - p.x, ..., every step rounded, whatever the grid's cell size.
  *   idx_bits    32 or 64: element type of idx_out ([nq][k] row-major)
- *   sorted_ids  0: indices in the caller's original order, 1: indices in the grid's spatial order
- *   exclude_self  1: query i is snapshot point i; drop it (torch_cluster.knn_graph loop=False semantics)
- *   d2_out      nullable fp32 [nq][k] squared distances */
+ *   sorted_ids  0: indices in the caller's original order, equal d² in ascending original index; 1: indices are ranks
+ *               in the grid's spatial order (pcd_grid_perm maps them back), and equal d² come in ascending RANK --
+ *               so the points of perm[rank] can differ from the sorted_ids = 0 list inside a group of exact ties
+ *   exclude_self  1: query i is snapshot point i; drop it (torch_cluster.knn_graph loop=False semantics).  Entry i is
+ *               dropped from the k + 1 best; a point with k + 1 or more exact duplicates of smaller index is not
+ *               among them and loses the last of them instead.  Needs k + 1 <= min(n, pcd_max_k()), sorted_ids = 0
+ *   d2_out      nullable fp32 [nq][k] squared distances
+ * Tested bit for bit against brute force on every row of translated, degenerate (line, plane, one point, n = 1),
+ * clustered, tied and 1e-18-scaled clouds for every k of the capacity ladder's rungs (tests/test_gpu_knn_edges.py). */
 int pcd_knn(const pcd_grid* g, const float* q, int64_t nq, int k, void* idx_out, int idx_bits, int sorted_ids,
             int exclude_self, float* d2_out, void* stream);
 
 /* Radius selection over the frozen snapshot (scipy query_ball_point semantics: float64 ((dx²+dy²)+dz²) <= r²,
  * members in ascending ORIGINAL index).  Two calls: count [nq] (int64), then, with the caller's exclusive prefix
  * sums offsets [nq+1] and total = offsets[nq], fill idx_out [total] (int64).  fill synchronises `stream`.
- * radii: fp32 [nq] per query (the reference builds a torch.float radius tensor, Selector.py:233). */
+ * radii: fp32 [nq] per query (the reference builds a torch.float radius tensor, Selector.py:233), r = the fp32 value
+ * converted exactly: r < 0 or NaN selects nobody, r = 0 the exact duplicates of q, r = +inf every point.  The kernels walk
+ * every cell of the grid that the ball's box overlaps, occupied or not: a ball much larger than a sparse cloud's
+ * occupied region costs its box's cell count. */
 int pcd_radius_count(const pcd_grid* g, const float* q, int64_t nq, const float* radii, int64_t* counts,
                      void* stream);
 int pcd_radius_fill(const pcd_grid* g, const float* q, int64_t nq, const float* radii, const int64_t* offsets,
@@ -367,7 +377,9 @@ int pcd_denoiser_status(pcd_denoiser* dn, int* bits, void* stream);
 int pcd_denoiser_coverage_excess(pcd_denoiser* dn, float* band_excess, float* sphere_ratio, void* stream);
 /* The kNN list the last K1 stage stored (the snapshot's `cols` nearest of each point's current position, in
  * (distance, index) order = getKNNSelection's columns, Selector.py:235-246), in caller order with ORIGINAL snapshot
- * indices: out int64 [N][cols], cols <= the stored list length (max(k, k_update) of the last iteration). */
+ * indices: out int64 [N][cols], cols <= the stored list length (max(k, k_update) of the last iteration).  The loop
+ * works in its grid's spatial order: exactly equal fp32 d² come in ascending RANK of that grid (pcd_grid_perm), as
+ * pcd_knn's sorted_ids = 1 gives them, not in ascending original index. */
 int pcd_denoiser_lists(pcd_denoiser* dn, int64_t* out, int cols, void* stream);
 /* Parity probe of the fused NVT2 stage (off by default; enabling allocates [N] float4).  While on, every NVT2 stage
  * also writes, per row, the eigenvalues of the reference's normalised tensor T / Σw (Decompositionor.py:299-300:
