@@ -141,7 +141,16 @@ int pcd_knn_stats(const pcd_grid* g, const float* q, int64_t nq, int k, int vari
                   void* stream);
 
 /* ------------------------------------------------------------------ tensor voting (H5-H7, H15) */
-/* CSR selection: segment r has centre ci[r] and neighbours nbr[off[r] .. off[r+1]); all int64 (torch long). */
+/* CSR selection: segment r has centre ci[r] and neighbours nbr[off[r] .. off[r+1]); all int64 (torch long).
+ * Better-filtered NVT: w_ij = acos(|clamp(normalize(v_j - v_i) . n_j)|) > rho, T_i = sum w n_j n_j^T / sum w, every
+ * w := 1 when none votes; eigval [m][3] ascending, eigvec [m][3][3] columns.
+ *   - a member coincident with the centre (v_j == v_i, e.g. the centre itself) has c = 0: it votes iff
+ *     acos(0) > rho, i.e. for every rho < pi/2;  rho < 0: every member votes;  rho >= pi/2: none does (fallback)
+ *   - the weight is multiplied in (w n_j) n_j^T as in the reference, so a member with a NaN or infinite normal makes
+ *     the tensor of EVERY row that lists it NaN whether it votes or not (a NaN pair itself never votes for rho >= 0);
+ *     a zero normal votes like any other (c = 0) and adds nothing but its count to sum w
+ *   - an empty segment (off[r] == off[r+1]) is 0 / 0: NaN eigenvalues (and the eigenvectors eigh makes of a NaN
+ *     tensor: first row (1, 0, 0), the rest NaN) */
 int pcd_nvt_csr(const float* pos, const float* n, int64_t npts, const int64_t* ci, const int64_t* off,
                 const int64_t* nbr, int64_t m, float rho, float* eigval, float* eigvec, void* stream);
 /* Normal-filtered NVT (CPSD): w_ij = acos(clamp(n_i . n_j)) <= rho; T_i = sum w n_j n_j^T / sum w, or n_i n_i^T when
@@ -162,6 +171,10 @@ int pcd_classify(const float* eigval, int64_t m, float scale, float* features, i
  *   solver 0: the LAPACK ssyevd restatement (NVT1, the public ops) -> w [m][3] ascending, vec [m][3][3] columns
  *   solver 1: NVT2's fixed-sweep Jacobi on the hardware rcp/sqrt estimates -> w [m][3] ascending, vec [m][3] = the
  *             smallest eigenvalue's unit eigenvector (sign arbitrary; classes and edge_step use it through y yᵀ)
+ *             Its rotations use 1 / a_pq: an off-diagonal below ~2^-128 is skipped as negligible, which holds for
+ *             NVT2's tensors (sums of unit normals, trace >= 1) and not for a tensor that is subnormal as a whole;
+ *             the eigenvector is defined for lambda_max >= 2^-30 (below, any tensor, the zero one included, can give NaN).
+ *             NaN in -> all three eigenvalues NaN.
  * For tests: pins NVT2's solver against the LAPACK one on the same tensors. */
 int pcd_eigh3_batch(const float* t6, int64_t m, int solver, float* w, float* vec, void* stream);
 /* Covariance of the k neighbours nbr[i*k .. i*k+k) about their own mean; eigval [n][3], eigvec [n][3][3]. */
@@ -173,7 +186,14 @@ enum { PCD_STEP_FLAT = 0, PCD_STEP_EDGE = 1, PCD_STEP_FEATURE = 2, PCD_STEP_CORN
        PCD_STEP_DUMMY = 5 };
 /* One Denoiser.*_step over a CSR selection: out [m][3] new positions of the centres.
  * edge_vectors [npts][3] is required for PCD_STEP_EDGE only.  Uses a device workspace it allocates
- * internally for the global (flat/new) reductions; stream-ordered. */
+ * internally for the global (flat/new) reductions; stream-ordered.
+ *   - the step di = alpha (x - v_i) is taken iff |di| < d for edge, feature, corner and new (strict) and iff
+ *     |di| <= d for flat; a NaN step is never taken; a system with an exactly zero pivot (inv_ex's info != 0) keeps v_i
+ *   - flat and new reduce their global centre and delta over nbr[0 .. off[m]): off[0] must be 0.  delta = 0 (every
+ *     row one point) and a NaN position among the rows (NaN centre; the NaN distances are dropped, delta = 0) give
+ *     weights of 0 or NaN: flat moves nobody, new keeps v_i to rounding
+ *   - an empty segment: flat (0 / 0), edge and corner (zero system) keep v_i; feature and new solve (I + n n^T) x =
+ *     (I + n n^T) v_i, i.e. v_i to rounding */
 int pcd_step_csr(int kind, const float* pos, const float* n, const float* edge_vectors, int64_t npts,
                  const int64_t* ci, const int64_t* off, const int64_t* nbr, int64_t m, float d, float alpha,
                  float* out, void* stream);

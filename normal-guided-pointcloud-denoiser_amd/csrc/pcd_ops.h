@@ -50,9 +50,9 @@ PCD_DEV void for_neighbours(P pos, Nr nrm, int cnt, Nb nb, F&& f) {
 //
 // The binary vote is decided without sqrt, divisions or acos whenever that is safe: with e = dv . n_j and
 // sq = |dv|², the reference's |c| < cos(rho) is e² < cos²(rho)·sq (cos(rho) > 0; for rho >= π/2 no pair votes, and
-// cos² is taken as -1 so that none does).  Only pairs with |e² - cos²(rho)·sq| <= 4e-6·(1 + |n_j|₁)²·sq, or with
-// sq outside [1e-24, 1e30] (where F.normalize's eps or over/underflow matter), evaluate the reference expression
-// exactly; sq = 0 (the row's own entry: the snapshot point of a row is its current point's neighbour) has the
+// cos² is taken as -1 so that none does; for rho < 0 every pair votes, and cos² is taken as +inf).  Only pairs
+// with |e² - cos²(rho)·sq| <= 4e-6·(1 + |n_j|₁)²·sq, or with sq outside [1e-24, 1e30] (where F.normalize's eps or
+// over/underflow matter), evaluate the reference expression exactly; sq = 0 (the row's own entry: the snapshot point of a row is its current point's neighbour) has the
 // constant vote acos(0) > rho.  The margin covers the estimate's error: |c_est - c_ref| ~ 1e-6 and cos(rho) vs acos's own rounding
 // < 1e-6 give |c_est - cos(rho)| > 4e-6·(1 + |n_j|₁) whenever the squared test clears its margin, since
 // |c| + cos(rho) <= 1 + |n_j|₁; e² and cos²(rho)·sq are themselves within ~1e-7 of that scale.
@@ -73,7 +73,8 @@ PCD_DEV Sym3 nvt_tensor(P pos, Nr nrm, Vec3 vi, int cnt, Nb nb, float rho, NbF n
     float w00 = 0.f, w01 = 0.f, w02 = 0.f, w11 = 0.f, w12 = 0.f, w22 = 0.f;
     int wsum = 0;
     const float cthr = cosf(rho);
-    const float cthr2 = cthr > 0.f ? cthr * cthr : -1.f;
+    // rho < 0: acos(.) >= 0 > rho, every pair votes (+inf: e² < inf; an overflowed e² falls to the exact path)
+    const float cthr2 = rho < 0.f ? INFINITY : cthr > 0.f ? cthr * cthr : -1.f;
     const bool w_self = acosf(0.f) > rho;   // the vote of a coincident neighbour (every row lists itself)
     // Packed fp32 (v_pk_mul / v_pk_add on gfx950: two lanes of a register pair per instruction) for the pairs of
     // products and sums; every component is the same IEEE multiply / add in the same order as the scalar code.

@@ -42,20 +42,26 @@ def angle(a, b):
     return np.arctan2(s, c)
 
 
-def staged_iteration(pos0, n0, d, dev, k=K, ku=KU, inject_fn=None, inject_pos=None, inject_edge=None):
+def staged_iteration(pos0, n0, d, dev, k=K, ku=KU, inject_fn=None, inject_pos=None, inject_edge=None, exact=False,
+                     reductions=False):
     """One fused iteration driven stage by stage; returns the per-stage outputs in caller order.
     inject_fn: the reference's smoothed normals, written over K1's f_n before NVT2 (pcd_denoiser_unpack FIELD_FN);
     inject_pos: the reference's positions after phases 0 and 1, written over the current positions before phases 1
-    and 2 -- so that NVT2 and every phase are fed IDENTICAL inputs (SURVEY §8(c)'s single-step gates)."""
+    and 2 -- so that NVT2 and every phase are fed IDENTICAL inputs (SURVEY §8(c)'s single-step gates).
+    exact: the LAPACK-exact NVT2 mode (pcd_denoiser_set_exact_nvt2).  reductions: also return the flat / new phases'
+    global sums (red4_{ph}: Σx, Σy, Σz, count, float64) and delta (delta_{ph}, float32) as the stages reduced them."""
     pos_t = torch.as_tensor(np.ascontiguousarray(pos0)).to(dev)
     n_t = torch.as_tensor(np.ascontiguousarray(n0)).to(dev)
     grid = nat.Grid(pos_t, k_hint=k)
     fd = nat.FusedDenoiser(grid, max(k, ku))
     fd.load(pos_t, n_t)
     fd.set_probe(True)
+    if exact:
+        fd.set_exact_nvt2(True)
     p = nat.make_params(k=k, k_update=ku, d=d)
     N = len(pos0)
     red4 = torch.zeros(4, dtype=torch.float64, device=dev)
+    red1 = torch.zeros(1, dtype=torch.float32, device=dev) if reductions else None
     out = {}
     fd.stage(p, nat.STAGE_KNN_NVT1)
     fn1 = torch.empty((N, 3), device=dev)
@@ -83,7 +89,10 @@ def staged_iteration(pos0, n0, d, dev, k=K, ku=KU, inject_fn=None, inject_pos=No
         if p.phase_kind[ph] in (nat.STEP_FLAT, nat.STEP_NEW):
             fd.stage(p, nat.STAGE_PHASE_SUM, ph, red4)
             fd.stage(p, nat.STAGE_PHASE_CENTRE, ph, red4)
-            fd.stage(p, nat.STAGE_PHASE_MAXDIST, ph, None)
+            fd.stage(p, nat.STAGE_PHASE_MAXDIST, ph, red1)
+            if reductions:
+                out[f"red4_{ph}"] = red4.cpu().numpy().copy()
+                out[f"delta_{ph}"] = red1.cpu().numpy()[0]
         fd.stage(p, nat.STAGE_PHASE_APPLY, ph, None)
         q = torch.empty((N, 3), device=dev)
         fd.store(q)
